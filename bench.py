@@ -11,8 +11,17 @@ F/N per GPU (frame-parallel, all-to-all around each motion module): all ranks
 together run ONE video's denoising, so value = steps/s of the node (strong
 scaling).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...
+
+A plain run does only what the headline needs: set up, W warm-up steps, the K timed steps, one
+JSON line (`value`, `ms_per_step`, `step_mfma`, which is arithmetic on the step time).  Every
+measurement that takes a run of its own is behind `--full`: the `roofline` timings, the
+`cpu_baseline`, the `no_cfg` variant and (N > 1) the `replicas_control`; without `--full` those
+keys are null.  `--dump-outputs DIR` writes what the timed loop returned after its last step
+(DenoiseLoop.run's latents, float32) as DIR/latents.npy (DIR/latents_rank<r>.npy per rank when
+N > 1: each rank's frame shard); inputs and weights are seeded, so two builds run with the same
+arguments can be compared output for output.
 
 `--gpus N > 1` without a torch.distributed environment (no WORLD_SIZE) starts the N ranks
 itself — `python -m torch.distributed.run --nproc-per-node N` as a CHILD process, before this
@@ -23,7 +32,7 @@ the step; value = all ranks' steps / the slowest rank's time, labelled, never th
 `--dry-run` goes through the same launch / rendezvous / max-over-ranks path on the CPU (gloo)
 without a model, for the CPU tests of this contract.
 
-Also reported: `roofline` for the spatial self-attention kernel at level 1
+With `--full`, also reported: `roofline` for the spatial self-attention kernel at level 1
 (S=4096, d=40: the north-star kernel), timed with HIP events on its launch
 stream; `step_mfma` = the whole step's algorithmic FLOPs / step time vs the
 bf16 dense MFMA peak; `cpu_baseline` = the oracle (PyTorch-CPU fp32
@@ -208,6 +217,18 @@ def cpu_baseline(unet_gpu, cfg_name, frames_sample, frames_full):
                       f"attention core, 0.1 % of the FLOPs, is linear in frames; BASELINE.md §3)"}
 
 
+def dump_outputs(dirname, lat, world, rank):
+    """The latents the timed loop returned after its last step, as float32 .npy: latents.npy on
+    one GPU, latents_rank<r>.npy (this rank's frame shard) on several.  1 MiB for the full
+    workload's [1, 4, 16, 64, 64], far below the 64 MB a dump may take."""
+    import numpy as np
+    d = Path(dirname)
+    d.mkdir(parents=True, exist_ok=True)
+    arr = lat.detach().float().cpu().numpy()
+    assert arr.nbytes <= 64 << 20, f"output dump of {arr.nbytes} bytes"
+    np.save(d / ("latents.npy" if world == 1 else f"latents_rank{rank}.npy"), arr)
+
+
 def _free_port() -> int:
     import socket
     with socket.socket() as s:
@@ -294,6 +315,12 @@ def main():
     ap.add_argument("--config", default="full", choices=["full", "tiny"])
     ap.add_argument("--frames", type=int, default=None)
     ap.add_argument("--no-graph", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beside the headline: roofline kernel timings, CPU oracle "
+                         "baseline, the no-CFG variant, the replicas control (N>1); each has its own --no-* switch")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the latents the timed loop returned to DIR/latents.npy "
+                         "(float32; DIR/latents_rank<r>.npy per rank when N>1)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-frames", type=int, default=2)
     ap.add_argument("--attn-reps", type=int, default=20)
@@ -374,7 +401,8 @@ def main():
 
     def timed(lay_, ehs_, guidance, cfg_shard=None):
         """W untimed + K timed replays of a captured loop on this layout; the timed region is
-        bracketed by barrier + synchronize on both sides; returns (max-over-ranks seconds, loop)."""
+        bracketed by barrier + synchronize on both sides; returns (max-over-ranks seconds, loop,
+        what the last timed step returned)."""
         lp = DenoiseLoop(unet, sched, lat_all[:, :, lay_.frame_slice()].cuda(), ehs_.cuda(), guidance,
                          timesteps=ts, use_graph=not args.no_graph, cfg_shard=cfg_shard)
         lp.prime()
@@ -384,7 +412,7 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
         t_start = time.perf_counter()
-        lp.run(args.steps)
+        out = lp.run(args.steps)
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
@@ -394,9 +422,12 @@ def main():
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             el = tt.item()
         assert torch.isfinite(lp.lat).all(), "non-finite latents"
-        return el, lp
+        return el, lp, out
 
-    elapsed, loop = timed(lay, ehs, 7.5, lay.cfg_shard)
+    elapsed, loop, out = timed(lay, ehs, 7.5, lay.cfg_shard)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, world, rank)
+    del out
     log(f"[bench] graph={'yes' if loop.graph is not None else 'no'} {loop.graph_error or ''}")
     videos = world if replicas else 1           # independent videos the node denoised per step
     sps = videos * args.steps / elapsed
@@ -408,12 +439,12 @@ def main():
     # the B=1 (no-CFG, guidance 1) variant, labelled — same graph-captured
     # loop on the conditional half only
     nocfg = None
-    if not args.no_nocfg:
+    if args.full and not args.no_nocfg:
         # no CFG pair to split: frame-shard over all ranks
         lay1 = lay if lay.layout == "frame" else NodeLayout("frame", frames, cfg=False, world=world, rank=rank,
                                                              overlap_chunks=args.overlap, window=args.window)
         unet.dist = lay1.frame_shard
-        e1, lp1 = timed(lay1, ehs[1:], 1.0)
+        e1, lp1, _ = timed(lay1, ehs[1:], 1.0)
         del lp1
         nocfg = {"value": round(videos * args.steps / e1, 4), "unit": "denoising steps/s",
                  "ms_per_step": round(1e3 * e1 / args.steps, 3),
@@ -422,10 +453,10 @@ def main():
     # the "replicas only" upper-bound control beside a sharded run — every rank
     # denoises its own whole 16-frame video, no collective; labelled, never the headline
     rep = None
-    if world > 1 and not replicas and not args.no_replicas:
+    if args.full and world > 1 and not replicas and not args.no_replicas:
         lay_r = NodeLayout("frame", frames, cfg=True, world=1, rank=0)
         unet.dist = None
-        er, lpr = timed(lay_r, ehs, 7.5)
+        er, lpr, _ = timed(lay_r, ehs, 7.5)
         del lpr
         rep = {"value": round(world * args.steps / er, 4), "unit": "denoising steps/s (node, N videos)",
                "ms_per_step": round(1e3 * er / args.steps, 3), "scaling": "weak",
@@ -433,24 +464,26 @@ def main():
                          "(SURVEY §8e upper-bound control, not the headline)"}
     unet.dist = lay.frame_shard
 
-    imgs = (2 // lay.cfg_ranks) * fl  # images per rank in the CFG run
-    mqkv = None
-    if lay.frame_shard is None and lay.cfg_shard is None:  # one GPU: the step's own operands
-        mqkv, _ = capture_l1_attention(unet, fl, cfg["cross_attention_dim"])
-    roof = time_attention(imgs, args.attn_reps, torch.cuda.current_stream(), model_qkv=mqkv)
-    syn = time_attention(imgs, args.attn_reps, torch.cuda.current_stream())
-    st = time_attention(imgs, args.attn_reps, torch.cuda.current_stream(), stress=True)
-    roof["synthetic"] = {k: syn[k] for k in ("achieved", "frac", "avg_launch_ms")}
-    roof["stress"] = {k: st[k] for k in ("achieved", "frac", "avg_launch_ms")}
-    roof["inputs"] = (("q | k | v of the step's level-1 self-attention in the synthetic-weight model (one eager "
-                       "forward of the workload with its N(0, 0.02^2) random-init weights, t = 981; softmax scale "
-                       "folded into q by to_q) -- not a trained network's logit statistics") if mqkv is not None else
-                      "synthetic (multi-rank run)") + (
-                      "; `synthetic`: q, k, v ~ N(0, 1.5^2) with the scale folded (exp2 argument std ~3.2), "
-                      "rounds 1-3's roofline input; `stress`: the scale not folded (std ~14)")
-    roof["traffic"], roof["traffic_source"] = pmc_traffic(imgs)
-    roof["mfma_busy"], roof["mfma_busy_source"] = pmc_mfma_busy()
-    roof["kernel_src_hash"] = roof_src_hash()
+    roof = None
+    if args.full:
+        imgs = (2 // lay.cfg_ranks) * fl  # images per rank in the CFG run
+        mqkv = None
+        if lay.frame_shard is None and lay.cfg_shard is None:  # one GPU: the step's own operands
+            mqkv, _ = capture_l1_attention(unet, fl, cfg["cross_attention_dim"])
+        roof = time_attention(imgs, args.attn_reps, torch.cuda.current_stream(), model_qkv=mqkv)
+        syn = time_attention(imgs, args.attn_reps, torch.cuda.current_stream())
+        st = time_attention(imgs, args.attn_reps, torch.cuda.current_stream(), stress=True)
+        roof["synthetic"] = {k: syn[k] for k in ("achieved", "frac", "avg_launch_ms")}
+        roof["stress"] = {k: st[k] for k in ("achieved", "frac", "avg_launch_ms")}
+        roof["inputs"] = (("q | k | v of the step's level-1 self-attention in the synthetic-weight model (one eager "
+                           "forward of the workload with its N(0, 0.02^2) random-init weights, t = 981; softmax scale "
+                           "folded into q by to_q) -- not a trained network's logit statistics") if mqkv is not None else
+                          "synthetic (multi-rank run)") + (
+                          "; `synthetic`: q, k, v ~ N(0, 1.5^2) with the scale folded (exp2 argument std ~3.2), "
+                          "rounds 1-3's roofline input; `stress`: the scale not folded (std ~14)")
+        roof["traffic"], roof["traffic_source"] = pmc_traffic(imgs)
+        roof["mfma_busy"], roof["mfma_busy_source"] = pmc_mfma_busy()
+        roof["kernel_src_hash"] = roof_src_hash()
     gpu_tflop = STEP_TFLOP[cfg_name] * frames / (16 if cfg_name == "full" else 4) / (1 if replicas else world)
     step_tf = gpu_tflop / (ms * 1e-3)
     step_mfma = {"algorithmic_tflop_per_step_per_gpu": round(gpu_tflop, 3),
@@ -464,7 +497,7 @@ def main():
         step_mfma["executed_achieved"] = round((gpu_tflop - saved) / (ms * 1e-3), 1)
         step_mfma["executed_frac"] = round((gpu_tflop - saved) / (ms * 1e-3) / PEAK_BF16_TFLOPS, 4)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         log("[bench] timing the CPU oracle baseline ...")
         cpu = cpu_baseline(unet, cfg_name, min(args.cpu_frames, frames), frames)
 

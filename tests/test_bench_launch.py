@@ -71,6 +71,33 @@ def test_launcher_matching_world_size_accepted():
     assert line["n_gpus"] == 2 and line["layout"] == "replicas"
 
 
+def test_full_and_dump_outputs_are_accepted(tmp_path):
+    """--full and --dump-outputs are options of every mode; the dry run has no model, so it
+    writes nothing."""
+    p = _bench(["--gpus", "1", "--dry-run", "--full", "--dump-outputs", str(tmp_path / "o")], _env())
+    assert p.returncode == 0, p.stderr[-2000:]
+    assert _json_line(p.stdout)["n_gpus"] == 1
+    assert not (tmp_path / "o").exists()
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_its_latents(cuda, tmp_path):
+    """A plain run (no --full) times exactly --steps steps, leaves the side measurements null and
+    writes the last timed step's latents as float32 DIR/latents.npy (tiny config: 4 frames)."""
+    import numpy as np
+    p = _bench(["--gpus", "1", "--config", "tiny", "--steps", "2", "--warmup", "1",
+                "--dump-outputs", str(tmp_path / "o")], _env())
+    assert p.returncode == 0, p.stderr[-2000:]
+    line = _json_line(p.stdout)
+    assert line["steps"] == 2 and line["warmup"] == 1 and line["dtype"] == "bf16"
+    assert line["ms_per_step"] > 0 and abs(line["value"] * line["ms_per_step"] / 1e3 - 1) < 1e-2
+    for k in ("roofline", "cpu_baseline", "no_cfg", "replicas_control"):
+        assert line[k] is None, k
+    lat = np.load(tmp_path / "o" / "latents.npy")
+    assert lat.dtype == np.float32 and lat.shape == (1, 4, 4, 64, 64)
+    assert np.isfinite(lat).all() and lat.std() > 0
+
+
 def test_child_failure_propagates():
     """A rank that fails makes the launcher exit non-zero (no silent one-GPU result)."""
     p = _bench(["--gpus", "2", "--dry-run", "--steps", "-1"], _env())
