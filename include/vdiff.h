@@ -153,6 +153,25 @@ int vd_gemm_plan(const vd_gemm_desc* d, int32_t* kernel, int32_t* split);
  * few output tiles to fill 256 CUs are split along K into fp32 slabs that a
  * second kernel reduces (deterministic, no atomics) while applying the epilogue. */
 int64_t vd_gemm_ws_bytes(const vd_gemm_desc* d);
+/* The 64 x 64 level's FeedForward in one launch (csrc/ff.hip; C = 320, hidden = 1280 only, else
+ * VD_EUNSUPPORTED; any M >= 1):
+ *   out[m] = res[m] + b2 + W2 · bf16((h + bh) · gelu_erf(g + bg)),  [h | g] = W1' · x[m]
+ * x bf16 [M][C] rows (row stride ldx), w1 the GEGLU projection packed as vd_gemm's VD_ACT_GEGLU
+ * takes it ([2 hidden][C]: 16-row blocks hidden i, gate i, ...; contiguous), b1 fp32 [2 hidden] in the
+ * same order or NULL, w2 bf16 [C][hidden] contiguous, b2 fp32 [C] or NULL, res bf16 rows (ld_res) or
+ * NULL, out bf16 rows (ldc).  ln_fold_s != NULL folds the LayerNorm of x's rows into the GEGLU
+ * projection exactly as vd_gemm_desc.ln_fold_s does (w1 = W∘gamma, b1 = b + W·beta, ln_fold_s its
+ * fp32 row sums).  The hidden activation is never written; the output bits equal
+ * vd_gemm(VD_ACT_GEGLU) followed by vd_gemm(res) as planned for M = 131072 rows, and a row's result
+ * does not depend on M.  vd_ff_fused_takes: 1 where the product plan runs the fused launch in place
+ * of the two (C = 320, hidden = 4C, M >= 65536), else 0; no launch, no state.  It is asked about
+ * the shape alone: operands vd_ff_fused cannot address (row strides with M * ld * 2 >= 2^31 bytes,
+ * unaligned pointers, strides not a multiple of 8) are VD_EINVAL there, and such a caller runs
+ * the two vd_gemm launches itself. */
+int vd_ff_fused(const void* x, int64_t ldx, int64_t M, int64_t C, int64_t hidden, const void* w1,
+                const float* b1, const float* ln_fold_s, float ln_eps, const void* w2, const float* b2,
+                const void* res, int64_t ld_res, void* out, int64_t ldc, vd_stream_t stream);
+int vd_ff_fused_takes(int64_t M, int64_t C, int64_t hidden);
 /* ---------------------------------------------------------------- GroupNorm
  * torch GroupNorm over NHWC rows, for ResnetBlock2D.norm1/2 (eps 1e-5, +SiLU),
  * Transformer2DModel.norm (eps 1e-6) and the motion-module norm whose

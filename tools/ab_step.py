@@ -25,6 +25,8 @@ Switches:
              (M <= 4096: a rank's level-2 QKV; with FOLD_V6_GEGLU=1 also the GEGLU) against the
              unfolded norm -> v2 there;
   skinny     the time-embedding GEMMs (M = 2) on v9 against v1 (forced path 1);
+  ff_fused   the level-1 FeedForward as one launch (vd_ff_fused, ops.ff_fused_takes) against the two
+             launches (GEGLU, then ff2 + residual) the parent ran;
   gn_split   vd_gn_partial_g's records per image (ops.gn_image_splits) capped at GN_SPLIT_CAP
              (default 64) and at least GN_SPLIT_ROWS (default 16) rows each."""
 from __future__ import annotations
@@ -187,7 +189,13 @@ def set_fold_force_v6(unet, on, saved):
     LnFold.gemm = gemm if on else orig_gemm
 
 
-SWITCHES = {"ln_fold": set_ln_fold, "cfg_dedup": set_cfg_dedup, "mfold": set_mfold, "pfold": set_pfold,
+def set_ff_fused(unet, on, saved):
+    from vdiff import ops
+    orig = saved.setdefault("ff_fused_takes", ops.ff_fused_takes)
+    ops.ff_fused_takes = orig if on else (lambda M, C, hidden: False)
+
+
+SWITCHES = {"ln_fold": set_ln_fold, "ff_fused": set_ff_fused, "cfg_dedup": set_cfg_dedup, "mfold": set_mfold, "pfold": set_pfold,
             "fold_v6": set_fold_v6, "gn_apply": set_gn_apply, "gn_split": set_gn_split, "skinny": set_skinny, "gn_grec": set_gn_grec, "gn_mframe": set_gn_mframe, "gn_small": set_gn_small, "fold_force_v6": set_fold_force_v6}
 
 
@@ -234,7 +242,8 @@ def main():
         print(f"{args.switch} {arm}: world {args.world} frames/rank {fl}: median {v[len(v) // 2]:.3f} ms/step, "
               f"min {v[0]:.3f} (rounds {len(v)})", flush=True)
     print(json.dumps({"switch": args.switch, "world": args.world, "frames_local": fl,
-                      "ms_per_step": {a: sorted(round(x, 3) for x in v) for a, v in res.items()}}))
+                      "ms_per_step": {a: sorted(round(x, 3) for x in v) for a, v in res.items()},
+                      "ms_per_step_by_round": {a: [round(x, 3) for x in v] for a, v in res.items()}}))
 
 
 if __name__ == "__main__":

@@ -6,7 +6,9 @@ descriptors), arms interleaved, outputs compared bit for bit against the product
 
 Cases: the UNet's 3x3 convs at the 16-frame CFG batch (32 images) — stride 1 at every level,
 the channel-concat convs of the up blocks, a stride-2 downsample, a nearest-x2 upsample — and a
-(2+1)D temporal conv (kt = 3, ks = 1); GEMM_AB_CASES=geglu: the four GEGLU projections instead.
+(2+1)D temporal conv (kt = 3, ks = 1); GEMM_AB_CASES=geglu: the four GEGLU projections instead;
+GEMM_AB_CASES=ff: the level-1 FeedForward as vd_ff_fused's one launch against the two vd_gemm
+launches it replaces (product library only; GEMM_AB_FF_M=131072,16384,8192 for other row counts).
 
     python tools/gemm_ab.py --save NAME [--rev REV]   # here: tools/diag_gemm/src_NAME/ from git REV (default HEAD)
     python tools/gemm_ab.py --build                   # here (CPU): tools/diag_gemm/libvdiff_gemm_NAME.so
@@ -148,6 +150,68 @@ def run(rounds: int):
         print(f"{name:22s} {line}", flush=True)
 
 
+def run_ff(rounds: int, Ms=(131072,)):
+    """GEMM_AB_CASES=ff: the level-1 FeedForward as the one fused launch (vd_ff_fused) against the
+    sum of the two launches it replaces (GEGLU with the folded norm3, then ff2 + bias + residual),
+    product library only, same process, arms interleaved per round, outputs compared bit for bit.
+    GEMM_AB_FF_M=M1,M2 sets the row counts (default 131072; the rank shapes are 16384 and 8192)."""
+    sys.path[:0] = [str(ROOT), str(PKG)]
+    import torch
+    from vdiff import ops
+    from vdiff.models.layers import LnFold, pack_geglu
+
+    dev = "cuda"
+    g = torch.Generator(device=dev).manual_seed(0)
+    Cc, H = 320, 1280
+    norm = torch.nn.LayerNorm(Cc).to(dev)
+    w1 = 0.02 * torch.randn(2 * H, Cc, device=dev, generator=g)
+    b1 = 0.02 * torch.randn(2 * H, device=dev, generator=g)
+    fold = LnFold(norm, w1, b1, pack=pack_geglu)
+    w1p, b1p = pack_geglu(w1.to(torch.bfloat16)), pack_geglu(b1.float())
+    w2 = (0.02 * torch.randn(Cc, H, device=dev, generator=g)).to(torch.bfloat16)
+    b2 = 0.02 * torch.randn(Cc, device=dev, generator=g)
+    for M in Ms:
+        x = torch.randn(M, Cc, device=dev, generator=g).to(torch.bfloat16)
+        out = torch.empty_like(x)
+        hid = torch.empty(M, H, device=dev, dtype=torch.bfloat16)
+        for label, folded in (("folded", True), ("unfolded", False)):
+            if folded and not fold.runs(M, ops.ACT_GEGLU):
+                continue
+
+            def pair():
+                if folded:
+                    ops.gemm(x, fold.w, bias=fold.b, act=ops.ACT_GEGLU, ln_fold=(fold.s, fold.eps), out=hid)
+                else:
+                    ops.gemm(x, w1p, bias=b1p, act=ops.ACT_GEGLU, out=hid)
+                return ops.gemm(hid, w2, bias=b2, res=x, out=out)
+
+            def one():
+                if folded:
+                    return ops.ff_fused(x, fold.w, w2, b1=fold.b, b2=b2, res=x, ln_fold=(fold.s, fold.eps), out=out)
+                return ops.ff_fused(x, w1p, w2, b1=b1p, b2=b2, res=x, out=out)
+
+            want = pair().clone()
+            same = torch.equal(one(), want)
+            torch.cuda.synchronize()
+            arms_ = {"two launches": pair, "fused": one}
+            res = {a: [] for a in arms_}
+            for r in range(rounds + 1):
+                for a, fn in arms_.items():
+                    fn()
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    for _ in range(10):
+                        fn()
+                    e1.record()
+                    torch.cuda.synchronize()
+                    if r:
+                        res[a].append(e0.elapsed_time(e1) * 100.0)  # us per call
+            fl = 2.0 * M * Cc * 3 * H
+            line = "  ".join(f"{a} median {sorted(v)[len(v) // 2]:7.1f} us (min {min(v):7.1f} max {max(v):7.1f}, "
+                             f"{fl / sorted(v)[len(v) // 2] / 1e6:5.0f} TF/s)" for a, v in res.items())
+            print(f"L1 FeedForward M={M} {label:8s} {line}  fused {'bit-identical' if same else 'DIFFERS'}", flush=True)
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--save")
@@ -159,5 +223,7 @@ if __name__ == "__main__":
         save(a.save, a.rev)
     elif a.build:
         build()
+    elif os.environ.get("GEMM_AB_CASES") == "ff":
+        run_ff(a.rounds, tuple(int(m) for m in os.environ.get("GEMM_AB_FF_M", "131072").split(",")))
     else:
         run(a.rounds)

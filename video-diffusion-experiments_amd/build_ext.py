@@ -5,8 +5,9 @@ Used by __graft_entry__.build() (always a clean compile) and `python build_ext.p
 sources + flags differs from the one it was built with).  The hash is compiled into the
 library (vd_build_hash()) and vdiff._lib checks it against the tree at load time, so a
 pushed or stale .so is never used in place of the tracked sources.
-The .so links against libamdhip64.so.7 / librccl.so.1 by SONAME, so inside a process that
-imported torch first it binds to torch's bundled HIP runtime (one runtime, shared streams).
+The .so links against libamdhip64.so.7 by SONAME, so inside a process that imported torch
+first it binds to torch's bundled HIP runtime (one runtime, shared streams).  Nothing in csrc/
+calls RCCL (the collectives go through torch.distributed), so it is not linked.
 """
 from __future__ import annotations
 
@@ -68,7 +69,7 @@ def build(verbose: bool = True, jobs: int = 8, clean: bool = False) -> Path:
         objs = list(ex.map(lambda s: _compile(s, defs, verbose), srcs))
     tmp = LIB.with_suffix(".so.tmp")
     cmd = [HIPCC, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", str(tmp), *map(str, objs),
-           "-L/opt/rocm/lib", "-lrccl"]
+           "-L/opt/rocm/lib"]
     if verbose:
         print("[vdiff build]", " ".join(cmd), flush=True)
     subprocess.run(cmd, check=True)

@@ -1,7 +1,7 @@
 """ctypes binding of libvdiff_hip.so (the C ABI declared in include/vdiff.h).
 
-The library must be loaded AFTER `import torch` so its libamdhip64.so.7 /
-librccl.so.1 dependencies resolve (by SONAME) to the runtime torch already
+The library must be loaded AFTER `import torch` so its libamdhip64.so.7
+dependency resolves (by SONAME) to the runtime torch already
 loaded — one HIP runtime, so torch's hipStream_t handles are valid here.
 There is no fallback: if the library is missing every op raises.
 """
@@ -28,6 +28,9 @@ SIGNATURES = {
     "vd_gemm": ([c_vp, c_vp], c_i32),
     "vd_gemm_ws_bytes": ([c_vp], c_i64),
     "vd_gemm_plan": ([c_vp, c_vp, c_vp], c_i32),
+    "vd_ff_fused": ([c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64,
+                     c_vp], c_i32),
+    "vd_ff_fused_takes": ([c_i64, c_i64, c_i64], c_i32),
     "vd_gn_partial": ([c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_i64, c_i64, c_i32, c_vp, c_vp], c_i32),
     "vd_gn_finalize": ([c_vp, c_i64, c_i32, c_i64, c_i32, c_f32, c_vp, c_vp, c_vp, c_vp], c_i32),
     "vd_gn_finalize_g": ([c_vp, c_i64, c_i32, c_i64, c_i32, c_f32, c_vp, c_vp, c_vp, c_vp], c_i32),

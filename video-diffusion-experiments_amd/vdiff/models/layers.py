@@ -480,7 +480,14 @@ class FeedForward(nn.Module):
 
     def forward_rows(self, n, res, fold: Optional[LnFold] = None):
         """ff(n) + res; with `fold` (the block's norm3 folded into the GEGLU GEMM) n is the
-        un-normalised residual stream itself."""
+        un-normalised residual stream itself.  Where the plan takes the shape (the 64 x 64 level:
+        C = 320 at M >= 65536) GEGLU, ff2, bias and residual run as ONE launch (ops.ff_fused, the
+        hidden activation never written) — bit-identical to the two launches below."""
+        w1 = fold.w if fold is not None else self.net[0]._w
+        if ops.ff_fused_takes(n.shape[0], w1.shape[1], self._w2.shape[1]) and w1.shape[0] == 2 * self._w2.shape[1]:
+            if fold is not None:
+                return ops.ff_fused(n, fold.w, self._w2, b1=fold.b, b2=self._b2, res=res, ln_fold=(fold.s, fold.eps))
+            return ops.ff_fused(n, w1, self._w2, b1=self.net[0]._b, b2=self._b2, res=res)
         if fold is not None:
             g = fold.gemm(n, act=ops.ACT_GEGLU)
         else:

@@ -212,6 +212,52 @@ def gemm_ln(a, w, gamma, beta, *, eps=1e-5, pe=None, pe_div=1, pe_period=1, bias
     return out, ln_out
 
 
+def ff_fused_takes(M, C, hidden):
+    """Whether the product plan runs the FeedForward over M rows as the one fused launch
+    (vd_ff_fused_takes: C = 320, hidden = 4C, M at or above its gate).  M goes through the
+    plan_scaled / gemm_plan(plan_div) controls like every GEMM's, so a frame shard and its
+    unsharded replay decide alike."""
+    m = int(M) * _PLAN.plan_mul
+    if _PLAN.plan_div > 1 and m % _PLAN.plan_div == 0:
+        m //= _PLAN.plan_div
+    return bool(lib().vd_ff_fused_takes(m, int(C), int(hidden)))
+
+
+def ff_fused(x, w1, w2, *, b1=None, b2=None, res=None, ln_fold=None, out=None):
+    """out = res + b2 + w2 · bf16(GEGLU(w1' · x + b1)) in one launch (vd_ff_fused: C = 320,
+    hidden = 1280, any M): w1 is the packed GEGLU projection [2 hidden][C] (pack_geglu), w2
+    [C][hidden]; ln_fold = (s, eps) folds the LayerNorm of x's rows as gemm(ln_fold=) does.
+    Bit-identical to gemm(act=ACT_GEGLU) + gemm(res=) under the 131072-row plan; raises on any
+    other (C, hidden) — there is no fallback here."""
+    _dev(x, w1, w2, b1, b2, res, out)
+    M, C_ = x.shape
+    ldx = _rows(x)
+    if _rows(w1) != w1.shape[1] or _rows(w2) != w2.shape[1]:
+        raise ValueError("ff_fused weights must be contiguous")
+    hidden = w2.shape[1]
+    if w1.shape != (2 * hidden, C_) or w2.shape[0] != C_:
+        raise ValueError(f"ff_fused: w1 {tuple(w1.shape)} / w2 {tuple(w2.shape)} do not fit x with C={C_}")
+    for t, n in ((b1, 2 * hidden), (b2, C_)):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != n):
+            raise ValueError("ff_fused biases must be contiguous fp32 vectors")
+    if res is not None and tuple(res.shape) != (M, C_):
+        raise ValueError("ff_fused: res must have x's shape")
+    s, eps = (None, 0.0)
+    if ln_fold is not None:
+        s, eps = ln_fold
+        _dev(s)
+        if s.dtype != torch.float32 or not s.is_contiguous() or s.numel() != 2 * hidden:
+            raise ValueError("ln_fold s must be a contiguous fp32 vector of 2*hidden entries")
+    if out is None:
+        out = torch.empty(M, C_, device=x.device, dtype=BF16)
+    elif tuple(out.shape) != (M, C_):
+        raise ValueError("ff_fused: out must have x's shape")
+    check(lib().vd_ff_fused(_p(x), ldx, M, C_, hidden, _p(w1), _p(b1), _p(s), float(eps), _p(w2), _p(b2),
+                            _p(res), _rows(res) if res is not None else 0, _p(out), _rows(out), _stream()),
+          "vd_ff_fused")
+    return out
+
+
 def conv3x3(x, n_img, h_in, w_in, w, *, x1=None, stride=1, upsample=False, bias=None,
             rowbias=None, rb_div=1, res=None, act=ACT_NONE, out=None, out_f32=False):
     """3x3 pad-1 conv over NHWC rows x (+ channel-concat x1); w packed [Cout][3][3][Cin]."""
