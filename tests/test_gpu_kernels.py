@@ -741,14 +741,19 @@ def test_conv3x3_splitk(cuda):
 
 
 # ---------------------------------------------------------------- conv
-@pytest.mark.parametrize("case", ["s1", "s2", "up", "concat", "cin8", "cout4", "m128"])
+@pytest.mark.parametrize("case", ["s1", "s2", "up", "concat", "cin8", "cout4", "m128", "v1n128"])
 def test_conv3x3(cuda, case):
-    """m128: fewer output rows than one 256-row tile (a 1-2 image rank's level 4) -> 64x64 tiles."""
+    """m128: fewer output rows than one 256-row tile (a 1-2 image rank's level 4) -> 64x64 tiles.
+    cin8 (K = 72, no multiple of 32) runs v1's 128 x 64 conv tile; v1n128 its 128 x 128 one at
+    M = 130: two row tiles with a ragged edge, two K tiles (v1's 128 x 160 conv tile:
+    test_conv3x3_large[v1], test_conv3d_temporal_taps path 1)."""
     torch.manual_seed(1)
     n, h, w = 3, 12, 10
     c0, c1, co = 64, 0, 128
     if case == "m128":
         n, h, w, c0, co = 2, 8, 8, 256, 320
+    if case == "v1n128":
+        n, h, w, c0, co = 1, 13, 10, 8, 128
     stride, up = 1, False
     if case == "s2":
         stride = 2

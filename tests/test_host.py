@@ -10,7 +10,7 @@ from vdiff.models import UNetMotionModel
 
 
 def im2col_nhwc(x_nhwc, stride=1):
-    """K index = tap*Cin + ci, tap = 3*dy + dx: the order csrc/gemm.hip gathers."""
+    """K index = tap*Cin + ci, tap = 3*dy + dx: the order the conv loaders of csrc/gemm_v*.hip gather."""
     n, h, w, c = x_nhwc.shape
     xp = F.pad(x_nhwc, (0, 0, 1, 1, 1, 1))
     ho, wo = (h - 1) // stride + 1, (w - 1) // stride + 1

@@ -1,6 +1,6 @@
 """What bounds the v2 implicit-GEMM conv: timing-only ABLATIONS of gemm2_kernel's operand traffic
 (DIAGNOSTIC builds, wrong results, never the product library).  Each variant is spliced into a
-copy of csrc/gemm.hip at build time:
+copy of csrc/gemm_v2.hip at build time:
 
   a6   the A (activation) pieces of a k-tile cut from 32 to 6 (waves 0-5 issue one piece each):
        the traffic a halo-tiled conv would move per tap (a 6 x 66-pixel, 64-channel patch = 49.5
@@ -28,6 +28,7 @@ from pathlib import Path
 ROOT = Path(__file__).resolve().parents[1]
 PKG = ROOT / "video-diffusion-experiments_amd"
 OUT = ROOT / "tools" / "diag_build"
+G2_FILE = "gemm_v2.hip"  # the source that holds gemm2_kernel and its launch
 
 WAIT_OLD = """      if (nbw == C::NBMAX) wait_vm<C::NA + C::NBMAX>();
       else wait_vm<C::NA + C::NBMAX - 1>();"""
@@ -118,14 +119,15 @@ def build():
     for name, var in VARIANTS.items():
         src_dir = OUT / f"src_{name}"
         src_dir.mkdir(exist_ok=True)
-        (src_dir / "gemm.hip").write_text(instrument((B.CSRC / "gemm.hip").read_text(), var))
+        # only the file that holds gemm2_kernel is recompiled per variant; its headers come from csrc/
+        (src_dir / G2_FILE).write_text(instrument((B.CSRC / G2_FILE).read_text(), var))
         defs = ['-DVD_BUILD_HASH="diag"', f'-DVD_BUILD_ARCH="{B.ARCH}"', f"-I{B.CSRC}", f"-I{ROOT / 'include'}"]
-        obj = OUT / f"gemm_{name}.o"
-        subprocess.run([B.HIPCC, *B.CFLAGS, *defs, "-c", str(src_dir / "gemm.hip"), "-o", str(obj)], check=True)
-        objs = [str(obj)] + [str(p) for p in sorted(B.BUILD.glob("*.o")) if p.stem != "gemm"]
+        obj = OUT / f"gemm_v2_{name}.o"
+        subprocess.run([B.HIPCC, *B.CFLAGS, *defs, "-c", str(src_dir / G2_FILE), "-o", str(obj)], check=True)
+        objs = [str(obj)] + [str(p) for p in sorted(B.BUILD.glob("*.o")) if p.stem != Path(G2_FILE).stem]
         lib = OUT / f"libvdiff_{name}.so"
         subprocess.run([B.HIPCC, f"--offload-arch={B.ARCH}", "-shared", "-fPIC", "-o", str(lib), *objs,
-                        "-L/opt/rocm/lib", "-lrccl"], check=True)
+                        "-L/opt/rocm/lib"], check=True)
         print("built", lib)
 
 

@@ -1,6 +1,6 @@
 """Where the v2 GEMM's k-tile loop spends its cycles: a DIAGNOSTIC build of the library with
 s_memtime stamps in gemm2_kernel (cdna_hip_programming.md "In-kernel stamps"), never the product
-library: the stamps live HERE (STAMPS below) and are spliced into a copy of csrc/gemm.hip at build
+library: the stamps live HERE (STAMPS below) and are spliced into a copy of csrc/gemm_v2.hip at build
 time, so the shipping kernel carries no diagnostic code.  Read the SHARES, not the run time (the stamps' lgkmcnt(0) fences
 forbid overlaps the real kernel has).
 
@@ -22,6 +22,7 @@ ROOT = Path(__file__).resolve().parents[1]
 PKG = ROOT / "video-diffusion-experiments_amd"
 OUT = ROOT / "tools" / "diag_build"
 LIB = OUT / "libvdiff_diag.so"
+G2_FILE = "gemm_v2.hip"  # the source that holds gemm2_kernel and its launch
 
 
 # The stamps: (anchor inside gemm2_kernel, text inserted before it / after it).  Each anchor
@@ -64,7 +65,7 @@ TAIL = """  unsigned long long tend;
 
 
 def instrument(text: str) -> str:
-    """gemm.hip with the stamps spliced into gemm2_kernel (a diagnostic copy under diag_build/src)."""
+    """G2_FILE with the stamps spliced into gemm2_kernel (a diagnostic copy under diag_build/src)."""
     sig = "template <int BN, int MODE>\n__global__ __launch_bounds__(G2_NT, 1) void gemm2_kernel("
     i0 = text.index(sig)
     i1 = text.index("\n}\n", i0) + 1  # the kernel's closing brace (column 0)
@@ -86,7 +87,7 @@ def build():
     for f in B.CSRC.iterdir():
         if f.suffix in (".hip", ".h"):
             text = f.read_text()
-            (src_dir / f.name).write_text(instrument(text) if f.name == "gemm.hip" else text)
+            (src_dir / f.name).write_text(instrument(text) if f.name == G2_FILE else text)
     defs = ['-DVD_BUILD_HASH="diag"', f'-DVD_BUILD_ARCH="{B.ARCH}"', f"-I{B.CSRC}", f"-I{ROOT / 'include'}"]
     objs = []
     for src in sorted(src_dir.glob("*.hip")):
@@ -94,7 +95,7 @@ def build():
         subprocess.run([B.HIPCC, *B.CFLAGS, *defs, "-c", str(src), "-o", str(obj)], check=True)
         objs.append(str(obj))
     subprocess.run([B.HIPCC, f"--offload-arch={B.ARCH}", "-shared", "-fPIC", "-o", str(LIB), *objs,
-                    "-L/opt/rocm/lib", "-lrccl"], check=True)
+                    "-L/opt/rocm/lib"], check=True)
     print("built", LIB)
 
 

@@ -1,5 +1,6 @@
-"""Same-process A/B of the GEMM / implicit-GEMM conv library code (csrc/gemm.hip) against earlier
-forms of its source: each arm is a DIAGNOSTIC library built from a saved copy of gemm.hip (plus the
+"""Same-process A/B of the GEMM / implicit-GEMM conv library code (csrc/gemm*.hip) against earlier
+forms of its source: each arm is a DIAGNOSTIC library built from a saved copy of a revision's GEMM
+sources (gemm.hip alone, or gemm.hip with the per-family gemm_*.hip and gemm_common.h; plus the
 product's other objects), loaded RTLD_LOCAL beside the product library.  Every case runs through
 the real vdiff.ops API with the arm's library swapped in as vdiff._lib's handle (same plan, same
 descriptors), arms interleaved, outputs compared bit for bit against the product's.
@@ -7,6 +8,7 @@ descriptors), arms interleaved, outputs compared bit for bit against the product
 Cases: the UNet's 3x3 convs at the 16-frame CFG batch (32 images) — stride 1 at every level,
 the channel-concat convs of the up blocks, a stride-2 downsample, a nearest-x2 upsample — and a
 (2+1)D temporal conv (kt = 3, ks = 1); GEMM_AB_CASES=geglu: the four GEGLU projections instead;
+GEMM_AB_CASES=v1: the small shapes v1's 128 x 160 tiles take (text K/V projection, conv_in);
 GEMM_AB_CASES=ff: the level-1 FeedForward as vd_ff_fused's one launch against the two vd_gemm
 launches it replaces (product library only; GEMM_AB_FF_M=131072,16384,8192 for other row counts).
 
@@ -26,15 +28,24 @@ from pathlib import Path
 ROOT = Path(__file__).resolve().parents[1]
 PKG = ROOT / "video-diffusion-experiments_amd"
 OUT = ROOT / "tools" / "diag_gemm"  # git-ignored; not gpurun-ignored (the box loads these libs)
-REL = "video-diffusion-experiments_amd/csrc/gemm.hip"
+REL = "video-diffusion-experiments_amd/csrc"
+
+
+def is_gemm_source(name: str) -> bool:
+    """The GEMM sources of a revision: gemm.hip alone, or the per-family gemm*.hip / gemm*.h."""
+    return name.startswith("gemm") and name.endswith((".hip", ".h"))
 
 
 def save(name: str, rev: str):
     d = OUT / f"src_{name}"
     d.mkdir(parents=True, exist_ok=True)
-    src = subprocess.run(["git", "-C", str(ROOT), "show", f"{rev}:{REL}"], check=True, capture_output=True, text=True).stdout
-    (d / "gemm.hip").write_text(src)
-    print("saved", d / "gemm.hip", "from", rev)
+    git = ["git", "-C", str(ROOT)]
+    ls = subprocess.run([*git, "ls-tree", "--name-only", rev, REL + "/"], check=True, capture_output=True, text=True)
+    for f in (Path(p).name for p in ls.stdout.split()):
+        if is_gemm_source(f) or f == "common.h":
+            src = subprocess.run([*git, "show", f"{rev}:{REL}/{f}"], check=True, capture_output=True, text=True).stdout
+            (d / f).write_text(src)
+            print("saved", d / f, "from", rev)
 
 
 def arms():
@@ -45,14 +56,17 @@ def build():
     sys.path.insert(0, str(PKG))
     import build_ext as B
     for name in arms():
-        src = OUT / f"src_{name}" / "gemm.hip"
+        # the arm's own headers first (a quoted include looks beside the including file), then the tree's
         defs = ['-DVD_BUILD_HASH="diag"', f'-DVD_BUILD_ARCH="{B.ARCH}"', f"-I{B.CSRC}", f"-I{ROOT / 'include'}"]
-        obj = OUT / f"gemm_{name}.o"
-        subprocess.run([B.HIPCC, *B.CFLAGS, *defs, "-c", str(src), "-o", str(obj)], check=True)
-        objs = [str(obj)] + [str(p) for p in sorted(B.BUILD.glob("*.o")) if p.stem != "gemm"]
+        objs = []
+        for src in sorted((OUT / f"src_{name}").glob("*.hip")):
+            obj = OUT / f"{src.stem}_{name}.o"
+            subprocess.run([B.HIPCC, *B.CFLAGS, *defs, "-c", str(src), "-o", str(obj)], check=True)
+            objs.append(str(obj))
+        objs += [str(p) for p in sorted(B.BUILD.glob("*.o")) if not is_gemm_source(p.stem + ".hip")]
         lib = OUT / f"libvdiff_gemm_{name}.so"
         subprocess.run([B.HIPCC, f"--offload-arch={B.ARCH}", "-shared", "-fPIC", "-o", str(lib), *objs,
-                        "-L/opt/rocm/lib", "-lrccl"], check=True)
+                        "-L/opt/rocm/lib"], check=True)
         print("built", lib)
 
 
@@ -99,6 +113,13 @@ def run(rounds: int):
         geglu("L2 GEGLU 640->2x2560", n * 32 * 32, 2560, 640)
         geglu("L3 GEGLU 1280->2x5120", n * 16 * 16, 5120, 1280)
         geglu("L4 GEGLU 1280->2x5120", n * 8 * 8, 5120, 1280)
+    elif os.environ.get("GEMM_AB_CASES") == "v1":
+        # gemm_kernel<128, 160, dense>: the time-embedding MLP (M = the CFG batch, below one 64-row tile);
+        # gemm_kernel<128, 160, conv>: conv_in (K = 9 x 8 = 72 is no multiple of 32)
+        for kk in (320, 1280):
+            a, wt = rnd(2, kk), rnd(1280, kk, scale=kk ** -0.5)
+            cases.append((f"temb MLP {kk}->1280", lambda a=a, wt=wt: ops.gemm(a, wt), 2.0 * 2 * 1280 * kk))
+        conv("conv_in 8->320", 64, 64, 8, 320)
     else:
         conv("L1 conv 320->320", 64, 64, 320, 320)
         conv("L2 conv 640->640", 32, 32, 640, 640)

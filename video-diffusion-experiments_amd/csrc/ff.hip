@@ -5,7 +5,7 @@
 // launch re-read it for each of its 16 column tiles) and every output row is written whole by
 // one wave (v2's two 160-column tiles shared a 128-B line of each 640-B row).
 //
-// Orientation is gemm.hip's: the MFMA computes C^T = W · A^T (v_mfma_f32_16x16x32_bf16, weights
+// Orientation is gemm_common.h's: the MFMA computes C^T = W · A^T (v_mfma_f32_16x16x32_bf16, weights
 // as the A operand, 16 activation rows as the B operand), so after the GEGLU epilogue lane
 // (fr, fq) holds hidden values of ROW fr — a B-operand layout for a second MFMA over the hidden.
 //  * A workgroup is 8 waves; each wave owns 16 whole rows per pass: x (10 k-steps = 40 VGPRs)
@@ -30,7 +30,7 @@
 // pairs, pack2; then one fp32 accumulator per output over hidden k-steps 0..39 ascending, hidden
 // k in v2's MFMA k-slot, v2's epilogue (bias, + residual, bf16) — so the output bits equal
 // vd_gemm(GEGLU) + vd_gemm(res) under the 131072-row plan (tests/test_gpu_ff_fused.py).
-#include "common.h"
+#include "gemm_common.h"  // lds_void, u32x4, G2_OOB (the out-of-range buffer offset)
 
 namespace {
 
@@ -42,12 +42,8 @@ constexpr int FF_W2_BYTES = FF_C * 64;            // 20 KiB
 constexpr int FF_STAGE = FF_W1_BYTES + FF_W2_BYTES;
 constexpr int FF_VEC = (4 * FF_H + FF_C) * 4;     // bh, bg, sh, sg (hidden order), b2
 constexpr int FF_OROW = 160 * 2 + 16;             // staged half output row (bytes, padded)
-constexpr uint32_t FF_OOB = 0x80000000u;
 static_assert(FF_NW * 16 * FF_OROW <= FF_STAGE, "output staging reuses one ring stage");
 static_assert(2 * FF_STAGE + FF_VEC <= 160 * 1024, "LDS");
-
-typedef __attribute__((address_space(3))) void lds_void;
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 struct FfArgs {
   const bf16_t* x; const bf16_t* w1; const bf16_t* w2; const bf16_t* res; bf16_t* out;
@@ -128,7 +124,7 @@ __global__ __launch_bounds__(FF_NW * 64, 1) void ff_fused_kernel(const FfArgs a)
   bf16x8 x[FF_KS];
   auto load_x = [&](int rb) {
     const int m = rb * 16 + fr;
-    const uint32_t o = (rb < rb1 && m < M) ? (uint32_t)m * (uint32_t)(a.ldx * 2) + (uint32_t)(fq * 16) : FF_OOB;
+    const uint32_t o = (rb < rb1 && m < M) ? (uint32_t)m * (uint32_t)(a.ldx * 2) + (uint32_t)(fq * 16) : G2_OOB;
 #pragma unroll
     for (int ks = 0; ks < FF_KS; ++ks)
       x[ks] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rx, o + (uint32_t)(ks * 64), 0, 0));
@@ -262,7 +258,7 @@ __global__ __launch_bounds__(FF_NW * 64, 1) void ff_fused_kernel(const FfArgs a)
       const int m = r * 16 + fr;
 #pragma unroll
       for (int pr = 0; pr < FF_NB / 2; ++pr) {
-        const uint32_t off = (r < rb1 && m < M) ? (uint32_t)(m * a.ld_res + pr * 32 + wcol) * 2u : FF_OOB;
+        const uint32_t off = (r < rb1 && m < M) ? (uint32_t)(m * a.ld_res + pr * 32 + wcol) * 2u : G2_OOB;
         rsv[pr] = __builtin_amdgcn_raw_buffer_load_b128(rr, off, 0, 0);
       }
     }
@@ -298,7 +294,7 @@ __global__ __launch_bounds__(FF_NW * 64, 1) void ff_fused_kernel(const FfArgs a)
         const int q = it * 64 + lane, row = q / 20, ch = q - row * 20;
         const uint4 v = *(const uint4*)(obuf + row * FF_OROW + ch * 16);
         const int m = r * 16 + row;
-        const uint32_t off = (r < rb1 && m < M) ? (uint32_t)(m * a.ldc + half * 160 + ch * 8) * 2u : FF_OOB;
+        const uint32_t off = (r < rb1 && m < M) ? (uint32_t)(m * a.ldc + half * 160 + ch * 8) * 2u : G2_OOB;
         __builtin_amdgcn_raw_buffer_store_b128(u32x4{v.x, v.y, v.z, v.w}, ro, off, 0, 0);
       }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -309,7 +305,9 @@ __global__ __launch_bounds__(FF_NW * 64, 1) void ff_fused_kernel(const FfArgs a)
 
 inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
-int ff_num_cus() {  // the device's CU count, read once per process (as gemm.hip's read_num_cus)
+// the device's CU count, read once per process (as gemm.hip's num_cus; its own, so that this file
+// needs no symbol of the GEMM objects and links beside any of them, tools/gemm_ab.py)
+int ff_num_cus() {
   static const int cus = [] {
     int dev = 0, n = 0;
     if (hipGetDevice(&dev) == hipSuccess &&
@@ -328,7 +326,7 @@ int ff_num_cus() {  // the device's CU count, read once per process (as gemm.hip
 // rank's M = 16384 and 8192 (half a pass and less: the 40-chunk weight walk is not amortised)
 // it loses, 86 vs 69 us and 78 vs 43 us, so those keep the two launches.
 extern "C" int vd_ff_fused_takes(int64_t M, int64_t C, int64_t hidden) {
-  return C == FF_C && hidden == FF_H && M >= 65536 && M * FF_C * 2 < (int64_t)FF_OOB;
+  return C == FF_C && hidden == FF_H && M >= 65536 && M * FF_C * 2 < (int64_t)G2_OOB;
 }
 
 extern "C" int vd_ff_fused(const void* x, int64_t ldx, int64_t M, int64_t C, int64_t hidden, const void* w1,
@@ -343,8 +341,8 @@ extern "C" int vd_ff_fused(const void* x, int64_t ldx, int64_t M, int64_t C, int
   VD_CHECK_ARG(!b1 || al16(b1));
   VD_CHECK_ARG(!b2 || al16(b2));
   VD_CHECK_ARG(!ln_fold_s || (al16(ln_fold_s) && ln_eps >= 0.f));
-  VD_CHECK_ARG(M * ldx * 2 < (int64_t)FF_OOB && M * ldc * 2 < (int64_t)FF_OOB &&
-               (!res || M * ld_res * 2 < (int64_t)FF_OOB));
+  VD_CHECK_ARG(M * ldx * 2 < (int64_t)G2_OOB && M * ldc * 2 < (int64_t)G2_OOB &&
+               (!res || M * ld_res * 2 < (int64_t)G2_OOB));
   FfArgs a;
   a.x = (const bf16_t*)x; a.w1 = (const bf16_t*)w1; a.w2 = (const bf16_t*)w2; a.res = (const bf16_t*)res;
   a.out = (bf16_t*)out; a.b1 = b1; a.b2 = b2; a.s = ln_fold_s;

@@ -9,7 +9,7 @@
 // from their row stride H*W): each wave holds its own positions' 16 token rows of the normed
 // activations as register fragments, and for every head h that head's 3d rows of the fused QKV
 // weight stream through an LDS-DMA ring; Q_h|K_h|V_h of the wave's 16 tokens accumulate on
-// 16x16x32 MFMAs (C^T = W.A^T as in gemm.hip: lane (fr, fq) ends with frame fr, channels
+// 16x16x32 MFMAs (C^T = W.A^T as in gemm_common.h: lane (fr, fq) ends with frame fr, channels
 // 16a + 4fq + j), are rounded to bf16 into a per-wave scratch, and the 16-frame attention of
 // that position and head runs exactly as temporal_mfma_kernel does (S^T = K.Q^T, softmax in log2
 // units, O^T = V^T.P^T with V's ones column giving the row sum).  Only the normed rows are read
@@ -54,7 +54,7 @@ struct MqCfg {
 };
 
 // element offset inside a [rows][64] block, 16-byte chunks XOR-swizzled by (row & 7) so the
-// 16x16x32 fragment reads (ds_read_b128) are conflict-free (gemm.hip's lds_off)
+// 16x16x32 fragment reads (ds_read_b128) are conflict-free (gemm_common.h's lds_off)
 __device__ __forceinline__ int sw64(int row, int chunk) { return row * 64 + ((chunk ^ (row & 7)) << 3); }
 
 // ---------------------------------------------------------------- the kernel (round 3)
@@ -121,7 +121,7 @@ struct Mq2Cfg {
 // token) for 40 more VGPRs of token fragments and 32 of accumulators; the heads' attention runs
 // position by position through the same per-wave scratch.
 // LNF (round 5): the motion block's norm1 / norm2 (+ the sinusoidal PE by frame) folded in, as
-// gemm.hip's v8 LNF: x holds the UN-normalised rows, w = W_qkv∘gamma, and `tab` per head h the
+// gemm_v8.hip's LNF: x holds the UN-normalised rows, w = W_qkv∘gamma, and `tab` per head h the
 // 120 fp32 column sums s of w's rows of that head (q | k | v, 40 each) then, per frame f < 16,
 // the 120 values P[f] = W·(beta + pe[f]) — an 8 KiB table that rides the weight ring as one 1 KiB
 // LDS-DMA piece per wave with the head's first chunk (double-buffered in LDS).  Each wave's token

@@ -80,7 +80,7 @@ def pack_conv3d(wt: torch.Tensor) -> torch.Tensor:
 def pack_geglu(w: torch.Tensor) -> torch.Tensor:
     """Interleave the hidden/gate halves of GEGLU.proj in 16-row blocks
     (hidden block i, gate block i, ...) so both halves of an output column land
-    in one GEMM lane (csrc/gemm.hip VD_ACT_GEGLU)."""
+    in one GEMM lane (csrc/gemm_common.h gemm_epilogue, VD_ACT_GEGLU)."""
     n = w.shape[0] // 2
     h, g = w[:n], w[n:]
     shp = (n // 16, 16) + tuple(w.shape[1:])

@@ -82,22 +82,43 @@ def gemm_plan(path: int = 0, plan_div: int = 0):
         _PLAN.path, _PLAN.plan_div = old
 
 
-def _plan_controls(d):
-    d.path = _PLAN.path
-    m = d.M * _PLAN.plan_mul
+def _planned_m(M):
+    """The row count an M-row request is planned for under plan_scaled / gemm_plan(plan_div)."""
+    m = int(M) * _PLAN.plan_mul
     if _PLAN.plan_div > 1 and m % _PLAN.plan_div == 0:
         m //= _PLAN.plan_div
+    return m
+
+
+def _plan_controls(d):
+    d.path = _PLAN.path
+    m = _planned_m(d.M)
     if m != d.M:
         d.plan_m = m
+
+
+def _plan_query(d):
+    """(kernel, split) of vd_gemm_plan for descriptor d exactly as it stands (kernel 0 = refused)."""
+    k, sp = C.c_int32(0), C.c_int32(0)
+    check(lib().vd_gemm_plan(C.byref(d), C.byref(k), C.byref(sp)), "vd_gemm_plan")
+    return k.value, sp.value
 
 
 def gemm_plan_of(d):
     """(kernel, split) vd_gemm would run for descriptor d under the current gemm_plan controls
     (vd_gemm_plan; kernel 0 = refused)."""
     _plan_controls(d)
-    k, sp = C.c_int32(0), C.c_int32(0)
-    check(lib().vd_gemm_plan(C.byref(d), C.byref(k), C.byref(sp)), "vd_gemm_plan")
-    return k.value, sp.value
+    return _plan_query(d)
+
+
+def _ln_fold_probe(M, N, K, act, rowbias, w=256, ldw=None, s=256):
+    """The descriptor that asks the plan about a folded LayerNorm: dummy aligned operands (the
+    plan reads sizes and alignments only) unless the weights' own are given."""
+    d = GemmDesc(a0=256, lda0=K, k0=K, a_mode=A_DENSE, w=w, ldw=K if ldw is None else ldw, M=M, N=N, K=K,
+                 bias=256, act=act, out=256, ldc=N // 2 if act == ACT_GEGLU else N, ln_fold_s=s, ln_fold_eps=1e-5)
+    if rowbias:  # the motion block's PE by frame (LnFold(pe=...)): no v8 / v5 plan takes a row bias
+        d.rowbias, d.ld_rb, d.rb_div = 256, N, 1
+    return d
 
 
 def ln_fold_runs(M, w, s, *, act=ACT_NONE, rowbias=False):
@@ -107,12 +128,7 @@ def ln_fold_runs(M, w, s, *, act=ACT_NONE, rowbias=False):
     and runs the plain GEMM.  Decided by the library's own plan (with plan_div, so a frame shard
     and its unsharded replay decide alike)."""
     N, K = w.shape
-    nout = N // 2 if act == ACT_GEGLU else N
-    d = GemmDesc(a0=256, lda0=K, k0=K, a_mode=A_DENSE, w=_p(w), ldw=_rows(w), M=M, N=N, K=K, bias=256,
-                 act=act, out=256, ldc=nout, ln_fold_s=_p(s), ln_fold_eps=1e-5)
-    if rowbias:  # the motion block's PE by frame (LnFold(pe=...)): no v8 / v5 plan takes a row bias
-        d.rowbias, d.ld_rb, d.rb_div = 256, N, 1
-    return gemm_plan_of(d)[0] != 0
+    return gemm_plan_of(_ln_fold_probe(M, N, K, act, rowbias, w=_p(w), ldw=_rows(w), s=_p(s)))[0] != 0
 
 
 # row counts a folded LayerNorm is asked about at prepare time: the UNet's levels at 2-32 images
@@ -123,17 +139,8 @@ def ln_fold_shape_ok(N, K, *, act=ACT_NONE, rowbias=False):
     """Whether a folded LayerNorm (ln_fold_s) can run for an N x K Linear at any of the row counts
     the UNet gives it (LN_FOLD_PROBE_M, automatic plan): decides at prepare time which folded
     weights to build."""
-    nout = N // 2 if act == ACT_GEGLU else N
-    for M in LN_FOLD_PROBE_M:
-        d = GemmDesc(a0=256, lda0=K, k0=K, a_mode=A_DENSE, w=256, ldw=K, M=M, N=N, K=K, bias=256, act=act,
-                     out=256, ldc=nout, ln_fold_s=256, ln_fold_eps=1e-5)
-        if rowbias:
-            d.rowbias, d.ld_rb, d.rb_div = 256, N, 1
-        k, sp = C.c_int32(0), C.c_int32(0)
-        check(lib().vd_gemm_plan(C.byref(d), C.byref(k), C.byref(sp)), "vd_gemm_plan")
-        if k.value != 0:
-            return True
-    return False
+    # the automatic plan: asked as it stands, without the gemm_plan controls
+    return any(_plan_query(_ln_fold_probe(M, N, K, act, rowbias))[0] != 0 for M in LN_FOLD_PROBE_M)
 
 
 def _run_gemm(d, device, what):
@@ -146,6 +153,22 @@ def _run_gemm(d, device, what):
         d.ws, d.ws_bytes = ws.data_ptr(), nbytes
     check(lib().vd_gemm(C.byref(d), _stream()), what)
     return ws  # keep alive until the launch is enqueued (stream-ordered reuse is safe)
+
+
+def _set_epilogue(d, M, device, *, bias=None, rowbias=None, rb_div=1, res=None, act=ACT_NONE, out=None,
+                  out_f32=False, out_cols=None):
+    """Fill the fields every GEMM form shares — bias, row bias, residual, activation and the output
+    (allocated M x out_cols, default N, where not given) — validating the operands' layout, and
+    return the output."""
+    odt = torch.float32 if out_f32 else BF16
+    if out is None:
+        out = torch.empty(M, d.N if out_cols is None else out_cols, device=device, dtype=odt)
+    d.bias, d.rowbias = _p(bias), _p(rowbias)
+    d.ld_rb, d.rb_div = rowbias.stride(0) if rowbias is not None else 0, rb_div
+    d.res, d.ld_res = _p(res), _rows(res) if res is not None else 0
+    d.act = act
+    d.out, d.ldc, d.out_f32 = _p(out), _rows(out, odt), int(out_f32)
+    return out
 
 
 def gemm(a, w, *, a1=None, bias=None, rowbias=None, rb_div=1, res=None, act=ACT_NONE,
@@ -166,16 +189,10 @@ def gemm(a, w, *, a1=None, bias=None, rowbias=None, rb_div=1, res=None, act=ACT_
         raise ValueError("concat operand shapes do not add up to K")
     if a1 is None and k0 != K:
         raise ValueError(f"A has {k0} columns, W has K={K}")
-    nout = N // 2 if act == ACT_GEGLU else N
-    if out is None:
-        out = torch.empty(M, nout, device=a.device, dtype=torch.float32 if out_f32 else BF16)
     d = GemmDesc(a0=_p(a), lda0=lda0, k0=k0, a1=_p(a1), lda1=lda1, a_mode=A_DENSE,
-                 w=_p(w), ldw=_rows(w), M=M, N=N, K=K,
-                 bias=_p(bias), rowbias=_p(rowbias),
-                 ld_rb=rowbias.stride(0) if rowbias is not None else 0, rb_div=rb_div,
-                 res=_p(res), ld_res=_rows(res) if res is not None else 0, act=act,
-                 out=_p(out), ldc=_rows(out, torch.float32 if out_f32 else BF16),
-                 out_f32=int(out_f32))
+                 w=_p(w), ldw=_rows(w), M=M, N=N, K=K)
+    out = _set_epilogue(d, M, a.device, bias=bias, rowbias=rowbias, rb_div=rb_div, res=res, act=act, out=out,
+                        out_f32=out_f32, out_cols=N // 2 if act == ACT_GEGLU else N)
     if rmap is not None:
         d.rmap_n1, d.rmap_n2, d.rmap_inner = (int(v) for v in rmap)
     if ln_fold is not None:
@@ -198,16 +215,13 @@ def gemm_ln(a, w, gamma, beta, *, eps=1e-5, pe=None, pe_div=1, pe_period=1, bias
     N, K = w.shape
     if a.shape[1] != K:
         raise ValueError(f"A has {a.shape[1]} columns, W has K={K}")
-    if out is None:
-        out = torch.empty(M, N, device=a.device, dtype=BF16)
     if ln_out is None:
         ln_out = torch.empty(M, N, device=a.device, dtype=BF16)
     d = GemmDesc(a0=_p(a), lda0=_rows(a), k0=K, a1=None, lda1=0, a_mode=A_DENSE,
-                 w=_p(w), ldw=_rows(w), M=M, N=N, K=K, bias=_p(bias), rowbias=None, ld_rb=0, rb_div=1,
-                 res=_p(res), ld_res=_rows(res) if res is not None else 0, act=ACT_NONE,
-                 out=_p(out), ldc=_rows(out), out_f32=0,
+                 w=_p(w), ldw=_rows(w), M=M, N=N, K=K,
                  ln_gamma=_p(gamma), ln_beta=_p(beta), ln_eps=eps, ln_pe=_p(pe), ln_pe_div=pe_div,
                  ln_pe_period=pe_period, ln_out=_p(ln_out), ld_ln=_rows(ln_out))
+    out = _set_epilogue(d, M, a.device, bias=bias, res=res, out=out)
     _run_gemm(d, a.device, "vd_gemm(ln)")
     return out, ln_out
 
@@ -217,10 +231,7 @@ def ff_fused_takes(M, C, hidden):
     (vd_ff_fused_takes: C = 320, hidden = 4C, M at or above its gate).  M goes through the
     plan_scaled / gemm_plan(plan_div) controls like every GEMM's, so a frame shard and its
     unsharded replay decide alike."""
-    m = int(M) * _PLAN.plan_mul
-    if _PLAN.plan_div > 1 and m % _PLAN.plan_div == 0:
-        m //= _PLAN.plan_div
-    return bool(lib().vd_ff_fused_takes(m, int(C), int(hidden)))
+    return bool(lib().vd_ff_fused_takes(_planned_m(M), int(C), int(hidden)))
 
 
 def ff_fused(x, w1, w2, *, b1=None, b2=None, res=None, ln_fold=None, out=None):
@@ -273,18 +284,13 @@ def conv3x3(x, n_img, h_in, w_in, w, *, x1=None, stride=1, upsample=False, bias=
     M = n_img * h_out * w_out
     if x.shape[0] != n_img * h_in * w_in:
         raise ValueError("conv input rows != n_img*h*w")
-    if out is None:
-        out = torch.empty(M, N, device=x.device, dtype=torch.float32 if out_f32 else BF16)
     d = GemmDesc(a0=_p(x), lda0=_rows(x), k0=c0, a1=_p(x1),
                  lda1=_rows(x1) if x1 is not None else 0, a_mode=A_CONV3X3,
                  n_img=n_img, h_in=h_in, w_in=w_in, h_out=h_out, w_out=w_out,
                  stride=stride, upsample=int(bool(upsample)),
-                 w=_p(w), ldw=_rows(w), M=M, N=N, K=K,
-                 bias=_p(bias), rowbias=_p(rowbias),
-                 ld_rb=rowbias.stride(0) if rowbias is not None else 0, rb_div=rb_div,
-                 res=_p(res), ld_res=_rows(res) if res is not None else 0, act=act,
-                 out=_p(out), ldc=_rows(out, torch.float32 if out_f32 else BF16),
-                 out_f32=int(out_f32))
+                 w=_p(w), ldw=_rows(w), M=M, N=N, K=K)
+    out = _set_epilogue(d, M, x.device, bias=bias, rowbias=rowbias, rb_div=rb_div, res=res, act=act, out=out,
+                        out_f32=out_f32)
     _run_gemm(d, x.device, "vd_gemm(conv3x3)")
     return out, h_out, w_out
 
@@ -308,15 +314,12 @@ def conv3d(x, batch, frames_in, h_in, w_in, w, *, kt=3, ks=3, frames_out=None, t
     h_out, w_out = (h_in - 1) // stride + 1, (w_in - 1) // stride + 1
     n_img = batch * frames_out
     M = n_img * h_out * w_out
-    if out is None:
-        out = torch.empty(M, N, device=x.device, dtype=torch.float32 if out_f32 else BF16)
     d = GemmDesc(a0=_p(x), lda0=_rows(x), k0=cin, a1=None, lda1=0, a_mode=A_CONV3X3,
                  n_img=n_img, h_in=h_in, w_in=w_in, h_out=h_out, w_out=w_out, stride=stride, upsample=0,
-                 w=_p(w), ldw=_rows(w), M=M, N=N, K=K, bias=_p(bias), rowbias=_p(rowbias),
-                 ld_rb=rowbias.stride(0) if rowbias is not None else 0, rb_div=rb_div,
-                 res=_p(res), ld_res=_rows(res) if res is not None else 0, act=act,
-                 out=_p(out), ldc=_rows(out, torch.float32 if out_f32 else BF16), out_f32=int(out_f32),
+                 w=_p(w), ldw=_rows(w), M=M, N=N, K=K,
                  kt=kt, ks=ks, frames_in=frames_in, frames_out=frames_out, t_off=t_off)
+    out = _set_epilogue(d, M, x.device, bias=bias, rowbias=rowbias, rb_div=rb_div, res=res, act=act, out=out,
+                        out_f32=out_f32)
     _run_gemm(d, x.device, "vd_gemm(conv3d)")
     return out, h_out, w_out
 
@@ -565,6 +568,7 @@ def motion_qkv_takes(batch, frames, positions, heads, d):
     """Whether vd_motion_qkv_attention takes this shape (vd_motion_qkv_attention_takes; no launch).
     Under gemm_plan(plan_div=N) the question is asked for one of N frame shards (batch 1, the
     positions divided by N), so an unsharded replay folds the motion norms exactly where a shard would."""
+    # not _planned_m: the shard is (batch 1, positions / N), and without a shard batch stays as it is
     positions *= _PLAN.plan_mul
     if _PLAN.plan_div > 1 and (batch * positions) % _PLAN.plan_div == 0:
         batch, positions = 1, batch * positions // _PLAN.plan_div
