@@ -375,6 +375,47 @@ int vd_flow_warp_stats(const void* frames_u8, const float* flow, int64_t videos,
                        int32_t H, int32_t W, double* stats, void* workspace, int64_t workspace_bytes,
                        vd_stream_t stream);
 
+/* LPIPS over consecutive frames (experiments/06_measure_grid_search.py:122-154 LPIPSMetric =
+ * lpips.LPIPS(net='alex', version='0.1'), eval mode), exact fp32: every convolution runs on
+ * the f32-input MFMA (v_mfma_f32_16x16x4_f32, bit-for-bit a k-ordered fmaf chain), no split-K
+ * and no float atomics, so results are deterministic and an image's value does not depend on
+ * the rest of the batch.
+ *
+ * vd_conv2d_f32: y = [relu](conv2d(x, w) + bias), NHWC fp32.  x [N][H][W][Cin], w
+ *   [Cout][kh][kw][Cin], bias [Cout] or NULL, y [N][OH][OW][Cout] with OH = (H + 2 pad - kh) /
+ *   stride + 1 (OW alike), zero padding.  Cout % 64 == 0; Cin % 4 == 0 (x and w 16-byte aligned)
+ *   or Cin == 3; x and y below 2^31 elements.
+ * vd_lpips_layer: one tap's distance for `pairs` pairs of feature maps fa, fb [pairs][pixels][C]
+ *   fp32: n = f / (sqrt(sum_c f^2) + 1e-10) per pixel, d = mean over pixels of
+ *   sum_c lin[c] (n_a - n_b)^2; out[p] = d if !accumulate, out[p] += d otherwise (fp64).
+ *   C % 64 == 0, C <= 512; per-pixel sums fp32, across pixels fp64 in a fixed order through the
+ *   workspace (at least the byte count vd_lpips_layer_workspace returns for `pairs`; -1 on
+ *   pairs < 1).
+ * vd_lpips_pairs: frames_u8 [videos][frames][H][W][3] uint8 -> out [videos][frames-1] fp64 =
+ *   LPIPS(frame f, frame f+1).  Per image: x = 2 u / 255 - 1, (x - shift) / scale, the five
+ *   ReLU taps of AlexNet `features` (conv(3,64,11,s4,p2); pool; conv(64,192,5,p2); pool;
+ *   conv(192,384,3,p1); conv(384,256,3,p1); conv(256,256,3,p1); pool = MaxPool2d(3, 2)), computed
+ *   once per frame; per pair the sum of the five vd_lpips_layer distances.  H, W >= 31, frames
+ *   >= 2.  params: one fp32 blob, 16-byte aligned, 2,470,854 floats in this order:
+ *     conv weights 1..5, each [Cout][k][k][Cin]   at float offset 0, 23232, 330432, 993984, 1878720
+ *     conv biases 1..5  (64,192,384,256,256)      at 2468544, 2468608, 2468800, 2469184, 2469440
+ *     lin vectors 1..5  (64,192,384,256,256)      at 2469696, 2469760, 2469952, 2470336, 2470592
+ *     shift[3], scale[3]                           at 2470848, 2470851
+ *   workspace: at least the byte count vd_lpips_workspace returns for images = videos * frames,
+ *   device memory, 16-byte aligned (-1 on H or W < 31 or a batch whose buffers pass 2^31
+ *   elements). */
+int vd_conv2d_f32(const float* x, int64_t N, int32_t H, int32_t W, int32_t Cin, const float* w,
+                  const float* bias, int32_t Cout, int32_t kh, int32_t kw, int32_t stride,
+                  int32_t pad, int32_t relu, float* y, vd_stream_t stream);
+int64_t vd_lpips_layer_workspace(int64_t pairs);
+int vd_lpips_layer(const float* fa, const float* fb, int64_t pairs, int64_t pixels, int32_t C,
+                   const float* lin, double* out, int32_t accumulate, void* workspace,
+                   int64_t workspace_bytes, vd_stream_t stream);
+int64_t vd_lpips_workspace(int64_t images, int32_t H, int32_t W);
+int vd_lpips_pairs(const void* frames_u8, int64_t videos, int32_t frames, int32_t H, int32_t W,
+                   const float* params, double* out, void* workspace, int64_t workspace_bytes,
+                   vd_stream_t stream);
+
 /* ---------------------------------------------------------------- step glue
  * vd_timestep_embed: diffusers Timesteps(dim, flip_sin_to_cos=True, shift 0)
  *   (a12) -> bf16 [B][dim].  Timestep = ts[*step_idx] if step_idx else ts[b]; ts holds

@@ -2,6 +2,7 @@
 512x512 uint8 videos (the reference's grid search measured 78 of them), 1x MI355X.
 
     python tools/metrics_bench.py [--videos 78] [--reps 20]
+    python tools/metrics_bench.py --lpips [--reps 20] [--lpips-out profiles/lpips_bench.json]
 
 One JSON line: videos/s, the kernel's HBM roofline (algorithmic bytes = every frame byte
 read once, per launch / average launch time from HIP events on the launch stream, vs
@@ -22,11 +23,48 @@ import torch  # noqa: E402
 from vdiff import metrics  # noqa: E402
 
 
+LPIPS_GFLOP_PER_IMAGE = 7.3   # AlexNet's five convs at 512x512 (2 K M N each: 0.75 + 2.44 + 1.28 + 1.70 + 1.13)
+F32_MATRIX_PEAK_TF = 157.3    # v_mfma_f32_* (f32 in, f32 accumulate)
+
+
+def lpips_leg(reps: int, out_path=None):
+    """LPIPS (vdiff.metrics.LPIPS, synthetic weights) over 1 video of 16 x 512x512 frames: frames/s
+    and the achieved fp32 rate of the convolutions against the f32-matrix peak."""
+    g = torch.Generator(device="cuda").manual_seed(0)
+    x = torch.randint(0, 256, (1, 16, 512, 512, 3), device="cuda", dtype=torch.uint8, generator=g)
+    model = metrics.LPIPS.synthetic(0)
+    s = torch.cuda.current_stream()
+    for _ in range(3):
+        model(x)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record(s)
+    for _ in range(reps):
+        model(x)
+    e1.record(s)
+    e1.synchronize()
+    ms = e0.elapsed_time(e1) / reps
+    tf = 16 * LPIPS_GFLOP_PER_IMAGE / ms  # GFLOP / ms = TFLOP / s
+    rec = {"metric": "LPIPS (AlexNet, exact fp32 MFMA) over consecutive frames, frames/s",
+           "value": round(16 / (ms * 1e-3), 1), "unit": "frames/s", "ms_per_call": round(ms, 4),
+           "config": {"workload": "1 video x 16 frames x 512x512x3 uint8 per call (15 pairs), synthetic weights"},
+           "roofline": {"bound": "f32 matrix", "achieved": round(tf, 2), "peak": F32_MATRIX_PEAK_TF, "unit": "TFLOP/s",
+                        "frac": round(tf / F32_MATRIX_PEAK_TF, 4),
+                        "algorithmic_gflop_per_image": LPIPS_GFLOP_PER_IMAGE}}
+    print(json.dumps(rec))
+    if out_path:
+        Path(out_path).parent.mkdir(parents=True, exist_ok=True)
+        Path(out_path).write_text(json.dumps(rec, indent=1) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--videos", type=int, default=78)
     ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--lpips", action="store_true", help="run the LPIPS leg instead of the frame-sum leg")
+    ap.add_argument("--lpips-out", default=None, help="also write the LPIPS record to this JSON file")
     args = ap.parse_args()
+    if args.lpips:
+        return lpips_leg(args.reps, args.lpips_out)
     g = torch.Generator(device="cuda").manual_seed(0)
     x = torch.randint(0, 256, (args.videos, 16, 512, 512, 3), device="cuda", dtype=torch.uint8, generator=g)
     s = torch.cuda.current_stream()

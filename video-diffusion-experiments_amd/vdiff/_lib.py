@@ -61,6 +61,12 @@ SIGNATURES = {
                            c_vp, c_vp, c_i64, c_vp], c_i32),
     "vd_flow_warp_workspace": ([c_i64, c_i32], c_i64),
     "vd_flow_warp_stats": ([c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_i64, c_vp], c_i32),
+    "vd_conv2d_f32": ([c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp,
+                       c_vp], c_i32),
+    "vd_lpips_layer_workspace": ([c_i64], c_i64),
+    "vd_lpips_layer": ([c_vp, c_vp, c_i64, c_i64, c_i32, c_vp, c_vp, c_i32, c_vp, c_i64, c_vp], c_i32),
+    "vd_lpips_workspace": ([c_i64, c_i32, c_i32], c_i64),
+    "vd_lpips_pairs": ([c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp], c_i32),
     "vd_timestep_embed": ([c_vp, c_i64, c_vp, c_i64, c_i32, c_vp, c_vp], c_i32),
     "vd_pack_latents": ([c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_i32, c_vp, c_i64, c_f32, c_vp], c_i32),
     "vd_unpack_nhwc": ([c_vp, c_i32, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp], c_i32),

@@ -625,6 +625,53 @@ def softmax_rows(s, out=None):
     return out
 
 
+# ---------------------------------------------------------------- exact-fp32 conv / LPIPS tap
+def _f32(t, what):
+    if t.dtype != torch.float32:
+        raise ValueError(f"{what}: expected float32, got {t.dtype}")
+    return t.contiguous()
+
+
+def conv2d_f32(x, w, bias=None, stride=1, pad=0, relu=False, out=None):
+    """Exact-fp32 convolution on the f32-input MFMA: x NHWC [N, H, W, Cin], w OHWI
+    [Cout, kh, kw, Cin], bias [Cout] -> NHWC [N, OH, OW, Cout] (zero padding).  Cout % 64 == 0,
+    Cin % 4 == 0 or Cin == 3."""
+    _dev(x, w, bias, out)
+    x, w = _f32(x, "conv2d_f32 x"), _f32(w, "conv2d_f32 w")
+    bias = None if bias is None else _f32(bias, "conv2d_f32 bias")
+    if x.dim() != 4 or w.dim() != 4 or x.shape[3] != w.shape[3]:
+        raise ValueError(f"conv2d_f32: x {tuple(x.shape)} (NHWC) does not fit w {tuple(w.shape)} (OHWI)")
+    N, H, W, Cin = x.shape
+    Cout, kh, kw, _ = w.shape
+    if H + 2 * pad < kh or W + 2 * pad < kw:
+        raise ValueError(f"conv2d_f32: a {kh}x{kw} kernel does not fit {H}x{W} with padding {pad}")
+    OH, OW = (H + 2 * pad - kh) // stride + 1, (W + 2 * pad - kw) // stride + 1
+    if out is None:
+        out = torch.empty(N, OH, OW, Cout, device=x.device, dtype=torch.float32)
+    check(lib().vd_conv2d_f32(_p(x), N, H, W, Cin, _p(w), _p(bias), Cout, kh, kw, stride, pad, int(relu), _p(out),
+                              _stream()), "vd_conv2d_f32")
+    return out
+
+
+def lpips_layer(fa, fb, lin, out=None, accumulate=False):
+    """One LPIPS tap: feature maps fa, fb fp32 [pairs, pixels, C] and lin [C] -> fp64 [pairs], the
+    pixel mean of sum_c lin[c] (fa/|fa| - fb/|fb|)^2; added to `out` when accumulate."""
+    _dev(fa, fb, lin, out)
+    fa, fb, lin = _f32(fa, "lpips_layer fa"), _f32(fb, "lpips_layer fb"), _f32(lin, "lpips_layer lin")
+    if fa.dim() != 3 or fa.shape != fb.shape or lin.numel() != fa.shape[2]:
+        raise ValueError(f"lpips_layer: fa {tuple(fa.shape)}, fb {tuple(fb.shape)}, lin {tuple(lin.shape)}")
+    pairs, pixels, Cc = fa.shape
+    if out is None:
+        if accumulate:
+            raise ValueError("lpips_layer: accumulate needs an out tensor")
+        out = torch.empty(pairs, device=fa.device, dtype=torch.float64)
+    nb = lib().vd_lpips_layer_workspace(pairs)
+    ws = torch.empty(max(nb, 8), device=fa.device, dtype=torch.uint8)
+    check(lib().vd_lpips_layer(_p(fa), _p(fb), pairs, pixels, Cc, _p(lin), _p(out), int(accumulate), _p(ws), nb,
+                               _stream()), "vd_lpips_layer")
+    return out
+
+
 # ---------------------------------------------------------------- step glue
 def timestep_embed(ts, dim, step_idx=None, batch=None, out=None):
     _dev(ts, step_idx)
