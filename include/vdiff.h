@@ -432,7 +432,9 @@ int vd_lpips_pairs(const void* frames_u8, int64_t videos, int32_t frames, int32_
  *   sqrt(1-a_t), sqrt(a_prev), sqrt(1-a_prev)}, step = *step_idx (or 0 if
  *   NULL) clamped to the n_coef rows of the table; fp32 in diffusers' operation
  *   order, one rounding per op (bit-exact vs torch); optional x0_out (B,C,F,H,W) fp32; optional next_in = the packed
- *   bf16 UNet input of the next step (dup = ncfg) — a1 + a13 fused.
+ *   bf16 UNet input of the next step (dup = ncfg) — a1 + a13 fused.  next_in is written whole, as
+ *   vd_pack_latents writes it: ncfg * B*F*H*W contiguous rows of cpad channels, the padding
+ *   [C, cpad) zero — it need not have been packed (or initialised) before.
  * vd_euler_cfg_step: as vd_ddim_cfg_step, with the EulerDiscreteScheduler.step
  *   update (s_churn 0, epsilon; diffusers' fp32 order x0 = x - s*eps,
  *   d = (x - x0)/s, x += d*(s_next - s)) and coef[4*step] = {sigma, sigma_next,

@@ -13,6 +13,7 @@ import torch
 import torch.nn.functional as F
 import torch.nn.functional as F_
 
+from memframe import close_bf16, close_f32  # the tolerances, shared with tests/test_gpu_memframe.py
 from vdiff import ops
 from vdiff._lib import GemmDesc
 from vdiff.dist import block_transpose_reference, rev3_reference
@@ -24,20 +25,6 @@ BF = torch.bfloat16
 
 def bf(x):
     return x.to(BF)
-
-
-def close_bf16(got, want, rel=1 / 128, abs_frac=2e-3):
-    want = want.double().cpu()
-    got = got.double().cpu()
-    scale = want.abs().max().item() + 1e-12
-    err = (got - want).abs()
-    bound = rel * want.abs() + abs_frac * scale
-    bad = (err > bound).sum().item()
-    assert bad == 0, f"{bad} / {want.numel()} elements out of tolerance; max err {err.max().item():.3e} (scale {scale:.3e})"
-
-
-def close_f32(got, want, rtol=1e-3, atol=1e-4):
-    torch.testing.assert_close(got.double().cpu(), want.double().cpu(), rtol=rtol, atol=atol)
 
 
 def rnd(*shape, std=1.0, dev="cuda"):

@@ -75,6 +75,17 @@ __global__ void unpack_kernel(const void* src, int src_f32, int64_t ld, int64_t 
   }
 }
 
+// next_in is the whole packed UNet input, as vd_pack_latents writes it: the channel padding
+// [C, cpad) of a row is zero.  The thread of the row's channel 0 writes it, so a next_in that
+// was never packed before (a fresh allocation) is fully defined after the step.
+__device__ __forceinline__ void zero_pad_cols(bf16_t* next_in, int64_t r, int64_t half_rows, int ncfg, int64_t C,
+                                              int64_t cpad) {
+  for (int64_t c = C; c < cpad; ++c) {
+    next_in[r * cpad + c] = 0;
+    if (ncfg == 2) next_in[(r + half_rows) * cpad + c] = 0;
+  }
+}
+
 // fp32 in diffusers' operation order with one rounding per operation (no contraction,
 // correctly rounded division), as torch's separate fp32 ops: bit-exact vs oracle/ddim_ref.py.
 __global__ void ddim_cfg_kernel(const float* eps, int64_t ld_eps, int ncfg, float g, float* lat,
@@ -107,6 +118,7 @@ __global__ void ddim_cfg_kernel(const float* eps, int64_t ld_eps, int ncfg, floa
       const bf16_t v = f2bf(xn);
       next_in[r * cpad + c] = v;
       if (ncfg == 2) next_in[(r + half_rows) * cpad + c] = v;
+      if (c == 0) zero_pad_cols(next_in, r, half_rows, ncfg, C, cpad);
     }
   }
 }
@@ -147,6 +159,7 @@ __global__ void euler_cfg_kernel(const float* eps, int64_t ld_eps, int ncfg, flo
       const bf16_t v = f2bf(div_rn(xn, in_div));
       next_in[r * cpad + c] = v;
       if (ncfg == 2) next_in[(r + half_rows) * cpad + c] = v;
+      if (c == 0) zero_pad_cols(next_in, r, half_rows, ncfg, C, cpad);
     }
   }
 }
