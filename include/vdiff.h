@@ -70,8 +70,10 @@ const char* vd_build_arch(void);
  *   gate); out has N/2 columns: h * gelu_erf(g)  (diffusers GEGLU, a10).
  */
 enum { VD_A_DENSE = 0, VD_A_CONV3X3 = 1 };
-enum { VD_ACT_NONE = 0, VD_ACT_SILU = 1, VD_ACT_GEGLU = 2, VD_ACT_GELU = 3 };
-/* VD_ACT_GELU: pointwise gelu (erf form) — the DiT MLP (build-defined, §8f rank 3). */
+enum { VD_ACT_NONE = 0, VD_ACT_SILU = 1, VD_ACT_GEGLU = 2, VD_ACT_GELU = 3, VD_ACT_QUICK_GELU = 4 };
+/* VD_ACT_GELU: pointwise gelu (erf form) — the DiT MLP (build-defined, §8f rank 3).
+ * VD_ACT_QUICK_GELU: x * sigmoid(1.702 x) in fp32 — the CLIP text encoder's MLP (SD-1.5's
+ * hidden_act "quick_gelu"); planned exactly as VD_ACT_GELU. */
 
 typedef struct vd_gemm_desc {
   const void* a0; int64_t lda0; int64_t k0;
@@ -277,7 +279,13 @@ int vd_attention_f32(const void* q, int64_t ldq, const void* k, int64_t ldk, con
  * 3 = flash40 / flash80 wherever they apply (d = 40 / 80, >= 2 key tiles); a kernel that does not
  * take the shape falls through to the next one down.  All of
  * them compute softmax(q k^T * scale) v; flash40 is bit-identical to flash32 (the parity tests
- * run each).  out_f32 as vd_attention_f32. */
+ * run each).  out_f32 as vd_attention_f32.
+ * VD_ATTN_CAUSAL OR-ed into kernel: query i attends to keys j <= i only (the CLIP text encoder's
+ * self-attention).  It needs sq == skv and kv_div == 1 (else VD_EINVAL), scale > 0 (else
+ * VD_EINVAL) and d in {32, 64} (else VD_EUNSUPPORTED); it always runs the 16x16x32 flash kernel,
+ * whose causal instances skip the key tiles wholly above the diagonal.  Any other bit above the
+ * low byte is VD_EINVAL.  vd_attention and vd_attention_f32 are never causal. */
+enum { VD_ATTN_CAUSAL = 0x100 };
 int vd_attention_ex(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
                     void* o, int64_t ldo, int64_t batch, int32_t heads, int64_t sq, int64_t skv, int32_t d,
                     int64_t kv_div, float scale, int32_t out_f32, int32_t kernel, vd_stream_t stream);

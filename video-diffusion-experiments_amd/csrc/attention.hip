@@ -92,7 +92,11 @@ __device__ __forceinline__ void kv_store(const stage_t<L>& st, bf16_t* kl, bf16_
   }
 }
 
-template <int D, int QBLK>
+// CAUSAL (compile time; the CLIP text encoder's self-attention, sq == skv): query i sees keys
+// j <= i.  A workgroup stops at the key tile that holds its last query (tiles wholly above the
+// diagonal are never loaded; the bound is workgroup-uniform because staging is cooperative), and
+// a wave masks the scores with key > query on the tiles that cross its diagonal.
+template <int D, int QBLK, bool CAUSAL = false>
 __global__ __launch_bounds__(NT, 2) void flash_attn_kernel(
     const bf16_t* __restrict__ q, int64_t ldq, const bf16_t* __restrict__ k, int64_t ldk,
     const bf16_t* __restrict__ v, int64_t ldv, bf16_t* __restrict__ o, int64_t ldo, int heads,
@@ -168,7 +172,13 @@ __global__ __launch_bounds__(NT, 2) void flash_attn_kernel(
 #pragma unroll
   for (int qb = 0; qb < QBLK; ++qb) { mrow[qb] = -INFINITY; lrow[qb] = 0.f; }
 
-  const int ntiles = (int)((skv + KT - 1) / KT);
+  int ntiles = (int)((skv + KT - 1) / KT);
+  if constexpr (CAUSAL) {  // stop at the tile of the workgroup's last query (blockIdx only: uniform)
+    int64_t qlast = ((int64_t)blockIdx.x + 1) * (4 * QWV) - 1;
+    if (qlast > sq - 1) qlast = sq - 1;
+    const int nt = (int)(qlast / KT) + 1;
+    if (nt < ntiles) ntiles = nt;
+  }
   const bool ragged = (skv % KT) != 0;
   kvst = kv_load<C::LREG>(kb_ptr, vb_ptr, ldk32, ldv32, 0, skv, krow, kcol);
   kv_store<C::LREG>(kvst, ks_lds[0], vs_lds[0], ldsk, ldsv);
@@ -219,6 +229,24 @@ __global__ __launch_bounds__(NT, 2) void flash_attn_kernel(
 #pragma unroll
             for (int qb = 0; qb < QBLK; ++qb) s[kb][qb][j] = -INFINITY;
           }
+    }
+    if constexpr (CAUSAL) {
+      // Wave-uniform test: the tile's last key lies above the wave's first query.  Tile 0 is
+      // always processed first and holds key 0 <= every query, so mrow is finite before any tile
+      // that is fully masked for this wave; there mx = -inf, mnew = mrow, p = 0, alpha = 1 and no
+      // exp2(-inf - -inf) can occur (c > 0 is checked by attention_entry).
+      if ((int64_t)t * KT + (KT - 1) > q0) {
+        const int64_t kbase = (int64_t)t * KT + 4 * fg;
+#pragma unroll
+        for (int qb = 0; qb < QBLK; ++qb) {
+          const int64_t qi = q0 + qb * 16 + fr;
+#pragma unroll
+          for (int kb = 0; kb < 4; ++kb)
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+              if (kbase + kb * 16 + j > qi) s[kb][qb][j] = -INFINITY;
+        }
+      }
     }
     // ---- online softmax in log2 units: p = exp2(s*c - m)
     bf16x8 pf[2][QBLK];
@@ -1755,6 +1783,28 @@ int launch_flash(const void* q, int64_t ldq, const void* k, int64_t ldk, const v
   return vd_launch_status();
 }
 
+// VD_ATTN_CAUSAL: always the 16x16x32 flash kernel's causal instances (d = 32 / 64), QBLK as above.
+template <int D>
+int launch_flash_causal(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
+                        void* o, int64_t ldo, int64_t batch, int heads, int64_t sq, float scale,
+                        hipStream_t s, int out_f32) {
+  const float c = scale * 1.4426950408889634f;
+  if constexpr (D <= 40) {
+    if (sq >= 1024) {
+      const dim3 grid((unsigned)((sq + 255) / 256), (unsigned)heads, (unsigned)batch);
+      hipLaunchKernelGGL((flash_attn_kernel<D, 4, true>), grid, dim3(NT), 0, s, (const bf16_t*)q, ldq,
+                         (const bf16_t*)k, ldk, (const bf16_t*)v, ldv, (bf16_t*)o, ldo, heads, sq, sq,
+                         (int64_t)1, c, out_f32);
+      return vd_launch_status();
+    }
+  }
+  const dim3 grid((unsigned)((sq + 127) / 128), (unsigned)heads, (unsigned)batch);
+  hipLaunchKernelGGL((flash_attn_kernel<D, 2, true>), grid, dim3(NT), 0, s, (const bf16_t*)q, ldq,
+                     (const bf16_t*)k, ldk, (const bf16_t*)v, ldv, (bf16_t*)o, ldo, heads, sq, sq,
+                     (int64_t)1, c, out_f32);
+  return vd_launch_status();
+}
+
 // ---------------------------------------------------------------- temporal
 // One wave per (b, p, h) item; lane = (query f = lane / LPQ, part = lane % LPQ);
 // 16-byte dim chunks c of the head are owned by part c % LPQ.
@@ -2221,8 +2271,16 @@ static int attention_entry(const void* q, int64_t ldq, const void* k, int64_t ld
   VD_CHECK_ARG(batch > 0 && heads > 0 && sq > 0 && skv > 0 && kv_div > 0 && batch % kv_div == 0);
   VD_CHECK_ARG(batch <= 65535 && heads <= 65535);
   VD_CHECK_ARG(skv * ldk < 0x7fffffff && skv * ldv < 0x7fffffff);
-  VD_CHECK_ARG(kernel >= 0 && kernel <= 3);
+  VD_CHECK_ARG(kernel >= 0 && (kernel & ~(0xff | VD_ATTN_CAUSAL)) == 0 && (kernel & 0xff) <= 3);
   hipStream_t s = (hipStream_t)stream;
+  if (kernel & VD_ATTN_CAUSAL) {
+    VD_CHECK_ARG(sq == skv && kv_div == 1 && scale > 0.f);
+    switch (d) {
+      case 32: return launch_flash_causal<32>(q, ldq, k, ldk, v, ldv, o, ldo, batch, heads, sq, scale, s, out_f32);
+      case 64: return launch_flash_causal<64>(q, ldq, k, ldk, v, ldv, o, ldo, batch, heads, sq, scale, s, out_f32);
+      default: return VD_EUNSUPPORTED;
+    }
+  }
   switch (d) {
     case 32: return launch_flash<32>(q, ldq, k, ldk, v, ldv, o, ldo, batch, heads, sq, skv, kv_div, scale, s, out_f32, kernel);
     case 40: return launch_flash<40>(q, ldq, k, ldk, v, ldv, o, ldo, batch, heads, sq, skv, kv_div, scale, s, out_f32, kernel);

@@ -86,8 +86,21 @@ __device__ __forceinline__ f32x2 gelu_erf2(f32x2 x) {
   const f32x2 erf = {copysignf(r[0], y[0]), copysignf(r[1], y[1])};
   return (0.5f * x) * (1.0f + erf);
 }
-// pointwise GEMM epilogue activation: VD_ACT_SILU or VD_ACT_GELU (erf form)
-__device__ __forceinline__ float act_pw(int act, float x) { return act == VD_ACT_GELU ? gelu_erf(x) : silu_f(x); }
+// true for the acts act_pw applies (one value in, one out, at the point of the epilogue where SiLU sits)
+__device__ __host__ __forceinline__ bool act_is_pw(int act) {
+  return act == VD_ACT_SILU || act == VD_ACT_GELU || act == VD_ACT_QUICK_GELU;
+}
+// CLIP's QuickGELU: x * sigmoid(1.702 x), the sigmoid formed as silu_f forms its own
+__device__ __forceinline__ float quick_gelu_f(float x) {
+  return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f((-1.702f * 1.4426950408889634f) * x));
+}
+// pointwise GEMM epilogue activation: VD_ACT_SILU, VD_ACT_GELU (erf form) or VD_ACT_QUICK_GELU.
+// Three separate (workgroup-uniform) branches on purpose: sharing one sigmoid path between SiLU
+// and QuickGELU (the factor as a scalar select) keeps the code smaller but cost 1-2 VGPRs in the
+// v2 / v3 / v4 / v8 kernels and a third spilled register in gemm4's conv instance.
+__device__ __forceinline__ float act_pw(int act, float x) {
+  return act == VD_ACT_GELU ? gelu_erf(x) : act == VD_ACT_QUICK_GELU ? quick_gelu_f(x) : silu_f(x);
+}
 
 template <typename T>
 __device__ __forceinline__ T wave_sum(T v) {

@@ -200,7 +200,7 @@ __device__ __forceinline__ void gemm_epilogue(const vd_gemm_desc& d, f32x4 (&acc
           o[0] += t0.x; o[1] += t0.y; o[2] += t0.z; o[3] += t0.w;
           o[4] += t1.x; o[5] += t1.y; o[6] += t1.z; o[7] += t1.w;
         }
-        if (d.act == VD_ACT_SILU || d.act == VD_ACT_GELU) {
+        if (act_is_pw(d.act)) {
 #pragma unroll
           for (int j = 0; j < 8; ++j) o[j] = act_pw(d.act, o[j]);
         }
@@ -236,7 +236,7 @@ __device__ __forceinline__ void gemm_epilogue(const vd_gemm_desc& d, f32x4 (&acc
         const float4 t = *(const float4*)(d.rowbias + (int64_t)rbr[b] * d.ld_rb + n);
         o[0] += t.x; o[1] += t.y; o[2] += t.z; o[3] += t.w;
       }
-      if (d.act == VD_ACT_SILU || d.act == VD_ACT_GELU) {
+      if (act_is_pw(d.act)) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) o[j] = act_pw(d.act, o[j]);
       }
@@ -370,7 +370,7 @@ __device__ __forceinline__ int epi_fast(const vd_gemm_desc& d, f32x4 (&acc)[NB][
         o[j] = __uint_as_float(r[0]) + bv[j];
         o[4 + j] = __uint_as_float(r[1]) + bv[4 + j];
       }
-      if (d.act == VD_ACT_SILU || d.act == VD_ACT_GELU) {
+      if (act_is_pw(d.act)) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) o[j] = act_pw(d.act, o[j]);
       }

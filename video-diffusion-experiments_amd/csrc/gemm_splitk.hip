@@ -50,7 +50,7 @@ __global__ __launch_bounds__(256) void gemm_splitk_reduce(const vd_gemm_desc d, 
         const float4 a = *(const float4*)(d.rowbias + (int64_t)drb(m32) * d.ld_rb + o);
         v[0] += a.x; v[1] += a.y; v[2] += a.z; v[3] += a.w;
       }
-      if (d.act == VD_ACT_SILU || d.act == VD_ACT_GELU)
+      if (act_is_pw(d.act))
         for (int j = 0; j < 4; ++j) v[j] = act_pw(d.act, v[j]);
       if (d.res) {
         const uint2 r = *(const uint2*)((const bf16_t*)d.res + mo * d.ld_res + o);

@@ -234,7 +234,7 @@ __global__ __launch_bounds__(G8_NW * 64, 1) void gemm8_kernel(const vd_gemm_desc
 #pragma unroll
         for (int jj = 0; jj < 8; ++jj) o[jj] += bv[jj];
       }
-      if (d.act == VD_ACT_SILU || d.act == VD_ACT_GELU) {
+      if (act_is_pw(d.act)) {
 #pragma unroll
         for (int jj = 0; jj < 8; ++jj) o[jj] = act_pw(d.act, o[jj]);
       }

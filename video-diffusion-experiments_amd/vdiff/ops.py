@@ -14,7 +14,7 @@ import torch
 
 from ._lib import VD_EUNSUPPORTED, GemmDesc, check, lib
 
-ACT_NONE, ACT_SILU, ACT_GEGLU, ACT_GELU = 0, 1, 2, 3
+ACT_NONE, ACT_SILU, ACT_GEGLU, ACT_GELU, ACT_QUICK_GELU = 0, 1, 2, 3, 4
 A_DENSE, A_CONV3X3 = 0, 1
 BF16 = torch.bfloat16
 
@@ -513,13 +513,16 @@ def layer_norm(x, gamma, beta, eps=1e-5, pe=None, pe_div=1, pe_period=1, out=Non
 
 # ---------------------------------------------------------------- attention
 ATTN_KERNELS = {"auto": 0, "v1": 1, "flash32": 2, "flash40": 3}
+ATTN_CAUSAL = 0x100  # VD_ATTN_CAUSAL, OR-ed into vd_attention_ex's kernel argument
 ATTN_TAP = None  # bench hook: callable(q, k, v, batch, heads, sq, skv, d, scale) seen by every attention call
 
 
-def attention(q, k, v, batch, heads, sq, skv, d, kv_div=1, scale=None, out=None, out_f32=False, kernel="auto"):
+def attention(q, k, v, batch, heads, sq, skv, d, kv_div=1, scale=None, out=None, out_f32=False, kernel="auto",
+              causal=False):
     """q/k/v: 2-D row views (may be column slices of a fused QKV buffer).  out_f32: O in fp32
     (the tests' north-star-tolerance mode).  kernel: "auto" (the product choice) or, for the
-    parity tests, "v1" / "flash32" / "flash40" (vd_attention_ex)."""
+    parity tests, "v1" / "flash32" / "flash40" (vd_attention_ex).  causal: query i attends to
+    keys j <= i (VD_ATTN_CAUSAL: sq == skv, kv_div == 1, d 32 or 64; the CLIP text encoder)."""
     _dev(q, k, v, out)
     if out is None:
         out = torch.empty(batch * sq, heads * d, device=q.device, dtype=torch.float32 if out_f32 else BF16)
@@ -527,8 +530,8 @@ def attention(q, k, v, batch, heads, sq, skv, d, kv_div=1, scale=None, out=None,
     if ATTN_TAP is not None:
         ATTN_TAP(q, k, v, batch, heads, sq, skv, d, scale)
     check(lib().vd_attention_ex(_p(q), q.stride(0), _p(k), k.stride(0), _p(v), v.stride(0), _p(out), out.stride(0),
-                                batch, heads, sq, skv, d, kv_div, scale, int(out_f32), ATTN_KERNELS[kernel],
-                                _stream()), "vd_attention_ex")
+                                batch, heads, sq, skv, d, kv_div, scale, int(out_f32),
+                                ATTN_KERNELS[kernel] | (ATTN_CAUSAL if causal else 0), _stream()), "vd_attention_ex")
     return out
 
 

@@ -19,9 +19,12 @@ num_inference_steps times with no host work in between.  The cross-attention
 K/V of the (constant) prompt embeddings are projected once per video, outside
 the graph.
 
-Out of scope: CLIP text encoding (a deterministic stub encoder
-stands in; real embeddings can be passed as prompt_embeds).  VAE decoding (§8f
-rank 1) runs when the pipeline holds a `vdiff.AutoencoderKL` (from_config builds one
+Text encoding: with a `vdiff.CLIPTextModel` and a `vdiff.CLIPTokenizer` (what from_pretrained
+loads from a directory's text_encoder/ and tokenizer/) encode_prompt is diffusers': tokenize to
+77 ids, one batched encoder forward for the positive and the negative prompts together,
+optional clip_skip.  Without a tokenizer the deterministic stub SyntheticTextEncoder stands in
+(from_config's synthetic pipelines); embeddings can always be passed as prompt_embeds.
+VAE decoding (§8f rank 1) runs when the pipeline holds a `vdiff.AutoencoderKL` (from_config builds one
 by default): output_type "pil" (diffusers' default: `.frames[0]` is the first video's
 list of PIL images, which 05_grid_search_ablation.py:169-182 saves as PNG / GIF),
 "pt" / "np" (diffusers' postprocessed video, (B, F, 3, H, W) tensor / (B, F, H, W, 3)
@@ -41,6 +44,7 @@ from collections import namedtuple
 import torch
 
 from . import ops
+from .models.clip import CLIPTextModel
 from .models.unet_motion import CIN_PAD, UNetMotionModel
 from .models.vae import AutoencoderKL
 from .sched.ddim import DDIMScheduler
@@ -50,8 +54,8 @@ AnimateDiffPipelineOutput = namedtuple("AnimateDiffPipelineOutput", ["frames"])
 
 
 class SyntheticTextEncoder:
-    """Stand-in for CLIPTextModel (out of scope): prompt -> deterministic
-    N(0,1) [77, dim] embedding seeded by crc32(prompt)."""
+    """Stand-in for CLIPTextModel where no tokenizer / weights are given (synthetic
+    pipelines): prompt -> deterministic N(0,1) [77, dim] embedding seeded by crc32(prompt)."""
 
     def __init__(self, dim: int, seq_len: int = 77):
         self.dim, self.seq_len = dim, seq_len
@@ -219,10 +223,14 @@ class AnimateDiffPipeline:
     # draws in that dtype
     latent_draw_dtype = torch.float16
 
-    def __init__(self, unet: UNetMotionModel, scheduler=None, text_encoder=None, vae=None, dist=None):
+    def __init__(self, unet: UNetMotionModel, scheduler=None, text_encoder=None, vae=None, dist=None,
+                 tokenizer=None):
         self.unet = unet
         self.scheduler = scheduler or DDIMScheduler()
         self.text_encoder = text_encoder or SyntheticTextEncoder(unet.config["cross_attention_dim"])
+        self.tokenizer = tokenizer
+        if tokenizer is not None and not isinstance(self.text_encoder, CLIPTextModel):
+            raise ValueError("tokenizer= needs text_encoder=vdiff.CLIPTextModel(...)")
         self.vae = vae
         self.dist = dist
         self.unet.dist = dist
@@ -254,9 +262,10 @@ class AnimateDiffPipeline:
                         device="cuda", dist=None, **unused):
         """diffusers AnimateDiffPipeline.from_pretrained(path, motion_adapter=, torch_dtype=) as
         05:130-134 calls it, over a LOCAL diffusers-layout directory (vdiff.pretrained): unet/
-        joined with the MotionAdapter's motion modules, vae/ (decoder), scheduler/.  The text
-        encoder stays the deterministic stub (CLIP is out of scope; pass prompt_embeds for real
-        embeddings).  device="cpu" builds the modules without preparing device operands."""
+        joined with the MotionAdapter's motion modules, vae/ (decoder), scheduler/, and — when
+        BOTH exist — text_encoder/ (vdiff.CLIPTextModel) with tokenizer/ (vdiff.CLIPTokenizer).
+        Without the two the text encoder stays the deterministic stub (pass prompt_embeds for
+        real embeddings).  device="cpu" builds the modules without preparing device operands."""
         from . import pretrained as P
         root = P._local_dir(pretrained_model_name_or_path, "AnimateDiffPipeline.from_pretrained")
         if motion_adapter is None:
@@ -264,11 +273,17 @@ class AnimateDiffPipeline:
         unet = P.load_unet_motion(root / "unet", motion_adapter, device=device, variant=variant)
         vae = P.load_vae(root / "vae", device=device, variant=variant) if (root / "vae").is_dir() else None
         sched = P.load_scheduler(root / "scheduler") if (root / "scheduler").is_dir() else None
+        enc = tok = None
+        if (root / "text_encoder").is_dir() and (root / "tokenizer").is_dir():
+            enc = P.load_text_encoder(root / "text_encoder", device=device, variant=variant)
+            tok = P.load_tokenizer(root / "tokenizer")
         if torch.device(device).type == "cuda":
             unet.prepare()
             if vae is not None:
                 vae.prepare()
-        pipe = cls(unet, sched, dist=dist, vae=vae)
+            if enc is not None:
+                enc.prepare()
+        pipe = cls(unet, sched, text_encoder=enc, dist=dist, vae=vae, tokenizer=tok)
         pipe.torch_dtype = torch_dtype
         return pipe
 
@@ -281,10 +296,24 @@ class AnimateDiffPipeline:
     def to(self, *a, **k):
         return self
 
-    def encode_prompt(self, prompt, batch):
+    def encode_prompt(self, prompt, batch, clip_skip=None):
+        """(batch, 77, dim) embeddings of a prompt or a list of prompts.  With a tokenizer and a
+        CLIPTextModel: the whole list is tokenized (padding="max_length", truncation) and encoded
+        in ONE batched forward; clip_skip as diffusers, final_layer_norm(hidden_states[-(clip_skip
+        + 1)]).  Without a tokenizer the stub encoder is called per prompt."""
         if isinstance(prompt, str):
             prompt = [prompt] * batch
-        return torch.stack([self.text_encoder(p) for p in prompt])
+        if self.tokenizer is None:
+            if clip_skip is not None:
+                raise ValueError("clip_skip needs a CLIPTextModel and a tokenizer")
+            return torch.stack([self.text_encoder(p) for p in prompt])
+        enc = self.text_encoder
+        ids = self.tokenizer(list(prompt), padding="max_length", max_length=self.tokenizer.model_max_length,
+                             truncation=True, return_tensors="pt").input_ids.to(enc.device)
+        if clip_skip is None:
+            return enc(ids)[0]
+        hs = enc(ids, output_hidden_states=True).hidden_states
+        return enc.text_model.final_layer_norm(hs[-(clip_skip + 1)])
 
     @torch.no_grad()
     def decode_latents(self, latents):
@@ -327,7 +356,7 @@ class AnimateDiffPipeline:
     def __call__(self, prompt=None, num_frames=16, height=None, width=None, num_inference_steps=50,
                  guidance_scale=7.5, negative_prompt=None, num_videos_per_prompt=1, eta=0.0,
                  generator=None, latents=None, prompt_embeds=None, negative_prompt_embeds=None,
-                 output_type="pil", return_dict=True, use_graph=True, **unused):
+                 output_type="pil", return_dict=True, use_graph=True, clip_skip=None, **unused):
         if eta != 0.0:
             raise NotImplementedError("eta > 0")
         if output_type not in ("latent", "pt", "np", "pil"):
@@ -338,17 +367,28 @@ class AnimateDiffPipeline:
         sample = self.unet.config["sample_size"]
         h = (height or sample * 8) // 8
         w = (width or sample * 8) // 8
+        do_cfg = guidance_scale > 1
         if prompt_embeds is None:
             if prompt is None:
                 raise ValueError("prompt or prompt_embeds required")
-            n = 1 if isinstance(prompt, str) else len(prompt)
-            prompt_embeds = self.encode_prompt(prompt, n)
+            pos = [prompt] if isinstance(prompt, str) else list(prompt)
+            n = len(pos)
+            if self.tokenizer is not None and do_cfg and negative_prompt_embeds is None:
+                # the positive and the negative prompts in one encoder forward
+                neg = negative_prompt if negative_prompt is not None else ""
+                neg = [neg] * n if isinstance(neg, str) else list(neg)
+                if len(neg) != n:
+                    raise ValueError(f"{len(neg)} negative prompts for {n} prompts")
+                both = self.encode_prompt(neg + pos, 2 * n, clip_skip=clip_skip)
+                negative_prompt_embeds = both[:n].repeat_interleave(num_videos_per_prompt, 0)
+                prompt_embeds = both[n:]
+            else:
+                prompt_embeds = self.encode_prompt(pos, n, clip_skip=clip_skip)
         B = prompt_embeds.shape[0] * num_videos_per_prompt
         prompt_embeds = prompt_embeds.repeat_interleave(num_videos_per_prompt, 0)
-        do_cfg = guidance_scale > 1
         if do_cfg:
             if negative_prompt_embeds is None:
-                negative_prompt_embeds = self.encode_prompt(negative_prompt or "", B)
+                negative_prompt_embeds = self.encode_prompt(negative_prompt or "", B, clip_skip=clip_skip)
             ehs = torch.cat([negative_prompt_embeds.to(prompt_embeds), prompt_embeds])
         else:
             ehs = prompt_embeds

@@ -182,6 +182,33 @@ def load_vae(vae_dir, device="cuda", variant=None):
                    what="AutoencoderKL")
 
 
+def load_text_encoder(enc_dir, device="cuda", variant=None):
+    """transformers' `text_encoder/` folder: config.json (CLIPTextConfig) + model[.variant].safetensors
+    -> vdiff.CLIPTextModel in bf16 on `device` (not prepared)."""
+    from safetensors.torch import load_file
+
+    from .models.clip import CLIPTextModel
+    d = _local_dir(enc_dir, "text_encoder")
+    cfg = read_json(d / "config.json")
+    if "CLIPTextModelWithProjection" in (cfg.get("architectures") or []):
+        raise NotImplementedError("CLIPTextModelWithProjection (SDXL's second encoder) is not built")
+    f = d / ("model" + (f".{variant}" if variant else "") + ".safetensors")
+    if not f.exists():
+        raise FileNotFoundError(f"no {f.name} in {d}")
+    with torch.device("meta"):
+        m = CLIPTextModel(cfg)
+    m = m.to_empty(device=device).to(dtype=torch.bfloat16)
+    sd = {k: v.to(torch.bfloat16) for k, v in load_file(str(f)).items()}
+    m.load_state_dict(sd, strict=True)
+    return m.eval()
+
+
+def load_tokenizer(tok_dir):
+    """The `tokenizer/` folder (vocab.json + merges.txt [+ tokenizer_config.json]) -> vdiff.CLIPTokenizer."""
+    from .tokenizer import CLIPTokenizer
+    return CLIPTokenizer.from_pretrained(_local_dir(tok_dir, "tokenizer"))
+
+
 def load_scheduler(sched_dir):
     """The pipeline's scheduler from scheduler_config.json.  SD-1.5 ships PNDMScheduler, which the
     reference immediately replaces (05:136-141 DDIM, 01/03 Euler) from `pipe.scheduler.config`;
