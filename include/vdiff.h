@@ -61,6 +61,14 @@ const char* vd_build_arch(void);
  *   lda1) — this is the up-block torch.cat([x, skip], 1) without materialising
  *   it.  stride 2 = Downsample2D; upsample 1 = Upsample2D (nearest x2 of the
  *   h_in x w_in input, then conv).  M = n_img*h_out*w_out.
+ *   stride 2 | VD_CONV_PAD_END = the VAE encoder's Downsample2D(padding=0): F.pad(x, (0, 1, 0, 1))
+ *   then a 3x3 stride-2 conv without padding — taps at input row 2*oh + dy, column 2*ow + dx
+ *   (dy, dx in 0..2), zero where that is >= h_in / w_in, so the zero band is at the far edge only.
+ *   h_out = (h_in - 2) / 2 + 1 and w_out alike (the pad-1 size for even inputs, one less for odd
+ *   ones).  The flag rides in `stride` because the struct cannot grow (its tail is pinned); it is
+ *   legal only as 2 | VD_CONV_PAD_END with kt <= 1, ks in {0, 3} and upsample 0, and any other
+ *   bit of `stride` above the low byte is VD_EINVAL.  The plan (kernel, split, workspace) is that
+ *   of plain stride 2.
  *   Replaces torch conv2d in ResnetBlock2D.conv1/conv2, Down/Upsample2D.conv,
  *   conv_in/conv_out and nn.Linear / 1x1 convs (a5, a8, a10).
  * epilogue, in order: + bias[n] (fp32) ; + rowbias[(m / rb_div) * ld_rb + n]
@@ -70,6 +78,7 @@ const char* vd_build_arch(void);
  *   gate); out has N/2 columns: h * gelu_erf(g)  (diffusers GEGLU, a10).
  */
 enum { VD_A_DENSE = 0, VD_A_CONV3X3 = 1 };
+enum { VD_CONV_PAD_END = 0x100 }; /* OR-ed into vd_gemm_desc.stride, see above */
 enum { VD_ACT_NONE = 0, VD_ACT_SILU = 1, VD_ACT_GEGLU = 2, VD_ACT_GELU = 3, VD_ACT_QUICK_GELU = 4 };
 /* VD_ACT_GELU: pointwise gelu (erf form) — the DiT MLP (build-defined, §8f rank 3).
  * VD_ACT_QUICK_GELU: x * sigmoid(1.702 x) in fp32 — the CLIP text encoder's MLP (SD-1.5's

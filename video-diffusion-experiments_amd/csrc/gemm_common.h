@@ -33,6 +33,17 @@ constexpr int G4_BM = 256, G4_BK = 32;
 constexpr int G6_BM = 64, G6_BN = 64, G6_NT = 256;
 constexpr int G8_BN = 160, G8_KMAX = 320, G8_NW = 8;
 
+// The conv kernels' MODE template argument is vd_gemm_desc.a_mode, or A_CONV_PAD_END for a
+// VD_A_CONV3X3 descriptor that came with stride 2 | VD_CONV_PAD_END (vd_gemm strips the flag, so
+// the kernels see d.stride == 2): instances of their own, so the pad-1 instances are unchanged.
+// A tap's input row is oh * stride + dy - conv_pad_lo (column alike); past the far edge the
+// loaders' range checks zero it in both modes.
+constexpr int A_CONV_PAD_END = 2;
+static_assert(A_CONV_PAD_END != VD_A_DENSE && A_CONV_PAD_END != VD_A_CONV3X3, "internal mode");
+template <int MODE>
+constexpr int conv_pad_lo = MODE == A_CONV_PAD_END ? 0 : 1;
+constexpr bool mode_is_conv(int mode) { return mode == VD_A_CONV3X3 || mode == A_CONV_PAD_END; }
+
 __device__ __forceinline__ int lds_off(int row, int chunk) {
   return row * BK + ((chunk ^ (row & 7)) << 3);
 }
@@ -411,6 +422,7 @@ struct Plan {
   int ver = 1;
   int bn = 128, split = 1;
   bool ln_fused = false;  // v5 writes ln_out in its epilogue
+  bool pad_end = false;   // the A_CONV_PAD_END instance; set by vd_gemm, not by the plan
   uint32_t a0b = 0, a1b = 0, wb = 0;
   int64_t ws_bytes = 0;
 };

@@ -46,7 +46,7 @@ __global__ __launch_bounds__(NT, 2) void gemm_kernel(const vd_gemm_desc d) {
   int pimg[RA], pfr[RA], poh[RA], pow_[RA];
   bool prow[RA];
   int cin = 0, hgrid = 0, wgrid = 0;
-  if constexpr (MODE == VD_A_CONV3X3) {
+  if constexpr (mode_is_conv(MODE)) {
     cin = (int)d.K / (d.ks * d.ks * d.kt);
     hgrid = d.upsample ? 2 * d.h_in : d.h_in;
     wgrid = d.upsample ? 2 * d.w_in : d.w_in;
@@ -94,8 +94,8 @@ __global__ __launch_bounds__(NT, 2) void gemm_kernel(const vd_gemm_desc d) {
       const int64_t ld = in0 ? d.lda0 : d.lda1;
 #pragma unroll
       for (int i = 0; i < RA; ++i) {
-        int ih = poh[i] * d.stride + dy - 1;
-        int iw = pow_[i] * d.stride + dx - 1;
+        int ih = poh[i] * d.stride + dy - conv_pad_lo<MODE>;
+        int iw = pow_[i] * d.stride + dx - conv_pad_lo<MODE>;
         const int fin = pfr[i] + dt;
         uint4 v = make_uint4(0, 0, 0, 0);
         if (kin && prow[i] && ih >= 0 && ih < hgrid && iw >= 0 && iw < wgrid && fin >= 0 && fin < d.frames_in) {
@@ -219,10 +219,12 @@ __global__ __launch_bounds__(G9_NW * 64) void gemm9_kernel(const vd_gemm_desc d)
 namespace vdgemm {
 
 template <int BM, int BN>
-static int launch(const vd_gemm_desc& d, hipStream_t s) {
+static int launch(const vd_gemm_desc& d, const Plan& p, hipStream_t s) {
   const int64_t tiles = ((d.M + BM - 1) / BM) * ((d.N + BN - 1) / BN);
   if (tiles > 0x7fffffff) return VD_EINVAL;
-  if (d.a_mode == VD_A_CONV3X3)
+  if (d.a_mode == VD_A_CONV3X3 && p.pad_end)
+    hipLaunchKernelGGL((gemm_kernel<BM, BN, A_CONV_PAD_END>), dim3((unsigned)tiles), dim3(NT), 0, s, d);
+  else if (d.a_mode == VD_A_CONV3X3)
     hipLaunchKernelGGL((gemm_kernel<BM, BN, VD_A_CONV3X3>), dim3((unsigned)tiles), dim3(NT), 0, s, d);
   else
     hipLaunchKernelGGL((gemm_kernel<BM, BN, VD_A_DENSE>), dim3((unsigned)tiles), dim3(NT), 0, s, d);
@@ -231,9 +233,9 @@ static int launch(const vd_gemm_desc& d, hipStream_t s) {
 
 int launch_v1(const vd_gemm_desc& d, const Plan& p, hipStream_t s) {
   switch (p.bn) {
-    case 128: return launch<128, 128>(d, s);
-    case 64: return launch<128, 64>(d, s);
-    case 160: return launch<128, 160>(d, s);
+    case 128: return launch<128, 128>(d, p, s);
+    case 64: return launch<128, 64>(d, p, s);
+    case 160: return launch<128, 160>(d, p, s);
     default: return VD_EINVAL;
   }
 }

@@ -61,7 +61,7 @@ __global__ __launch_bounds__(G2_NT, 1) void gemm2_kernel(const vd_gemm_desc d, u
       __builtin_amdgcn_make_buffer_rsrc((void*)(d.a1 ? d.a1 : d.a0), 0, d.a1 ? a1_bytes : 0, 0x00020000);
   const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)d.w, 0, w_bytes, 0x00020000);
   const int nbw = (C::NBI - wid + 7) / 8;  // this wave's B DMA instructions per K-tile
-  const int cin = MODE == VD_A_CONV3X3 ? (int)(K / (d.ks * d.ks * d.kt)) : 0;
+  const int cin = mode_is_conv(MODE) ? (int)(K / (d.ks * d.ks * d.kt)) : 0;
   const int hgrid = d.upsample ? 2 * d.h_in : d.h_in;
   const int wgrid = d.upsample ? 2 * d.w_in : d.w_in;
 
@@ -140,7 +140,8 @@ __global__ __launch_bounds__(G2_NT, 1) void gemm2_kernel(const vd_gemm_desc d, u
         // exec-mask branches per row (the && chain compiled to three nested saveexec blocks)
 #pragma unroll
         for (int j = 0; j < C::NA; ++j) {
-          const int ih = poh[j] * d.stride + dy - 1, iw = pow_[j] * d.stride + dx - 1;
+          const int ih = poh[j] * d.stride + dy - conv_pad_lo<MODE>,
+                    iw = pow_[j] * d.stride + dx - conv_pad_lo<MODE>;
           const int fin = pfr[j] + dt;
           const bool ok = ((uint32_t)ih < (uint32_t)hgrid) & ((uint32_t)iw < (uint32_t)wgrid) &
                           ((uint32_t)fin < (uint32_t)d.frames_in);
@@ -283,7 +284,9 @@ template <int BN>
 static int launch2(const vd_gemm_desc& d, const Plan& p, hipStream_t s) {
   const int64_t units = ((d.M + G2_BM - 1) / G2_BM) * ((d.N + BN - 1) / BN) * p.split;
   const dim3 grid((unsigned)persistent_grid(units));
-  if (d.a_mode == VD_A_CONV3X3)
+  if (d.a_mode == VD_A_CONV3X3 && p.pad_end)
+    hipLaunchKernelGGL((gemm2_kernel<BN, A_CONV_PAD_END>), grid, dim3(G2_NT), 0, s, d, p.a0b, p.a1b, p.wb, p.split);
+  else if (d.a_mode == VD_A_CONV3X3)
     hipLaunchKernelGGL((gemm2_kernel<BN, VD_A_CONV3X3>), grid, dim3(G2_NT), 0, s, d, p.a0b, p.a1b, p.wb, p.split);
   else
     hipLaunchKernelGGL((gemm2_kernel<BN, VD_A_DENSE>), grid, dim3(G2_NT), 0, s, d, p.a0b, p.a1b, p.wb, p.split);

@@ -211,9 +211,11 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, WM * WN * 64), amdgpu_w
   const int na_w = (C::NPA - wid + C::NW - 1) / C::NW;
   const int nb_w = (C::NPB - wid + C::NW - 1) / C::NW;
   const int per_step = na_w + nb_w;
-  const int cin = MODE == VD_A_CONV3X3 ? (int)(K / 9) : 0;
-  const int hgrid = d.upsample ? 2 * d.h_in : d.h_in;
-  const int wgrid = d.upsample ? 2 * d.w_in : d.w_in;
+  const int cin = mode_is_conv(MODE) ? (int)(K / 9) : 0;
+  // pad-end: stride 2 and no upsample are the mode itself (checked by vd_gemm), so constants here
+  const int cstride = MODE == A_CONV_PAD_END ? 2 : d.stride, cup = MODE == A_CONV_PAD_END ? 0 : d.upsample;
+  const int hgrid = cup ? 2 * d.h_in : d.h_in;
+  const int wgrid = cup ? 2 * d.w_in : d.w_in;
   // load-free epilogue (epi_fast) for plain bf16 outputs
   const bool fast = !LN && split == 1 && !d.res && !d.rowbias && !d.out_f32 && !d.rmap_inner && (N % 8) == 0 &&
                     (d.ldc % 8) == 0 && (((uintptr_t)d.out) & 15) == 0;
@@ -299,10 +301,11 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, WM * WN * 64), amdgpu_w
           const int dy = c_tap / 3, dx = c_tap - 3 * dy;
 #pragma unroll
           for (int j = 0; j < C::NAMAX; ++j) {
-            int ih = (pohw[j] >> 16) * d.stride + dy - 1, iw = (pohw[j] & 0xffff) * d.stride + dx - 1;
+            int ih = (pohw[j] >> 16) * cstride + dy - conv_pad_lo<MODE>,
+                iw = (pohw[j] & 0xffff) * cstride + dx - conv_pad_lo<MODE>;
             const bool ok = ((uint32_t)ih < (uint32_t)hgrid) & ((uint32_t)iw < (uint32_t)wgrid);  // branch-free
-            ih >>= d.upsample;
-            iw >>= d.upsample;
+            ih >>= cup;
+            iw >>= cup;
             const uint32_t pix = (uint32_t)(pimg[j] + ih * d.w_in + iw);
             aoff0[j] = ok ? pix * (uint32_t)(d.lda0 * 2) + lc16 : G2_OOB;
             aoff1[j] = ok ? pix * (uint32_t)(d.lda1 * 2) + lc16 : G2_OOB;
@@ -320,7 +323,7 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, WM * WN * 64), amdgpu_w
       for (int j = 0; j < C::NBMAX; ++j)
         if (j < nb_w) dma16(rw, lb + (wid + C::NW * j) * 1024, boff[j] + (uint32_t)kb * 2);
     }
-    if constexpr (MODE == VD_A_CONV3X3) {
+    if constexpr (mode_is_conv(MODE)) {
       c_ci += G4_BK;
       if (c_ci == cin) { c_ci = 0; ++c_tap; c_new = true; }
     }
@@ -465,7 +468,10 @@ static int launch4(const vd_gemm_desc& d, const Plan& p, hipStream_t s) {
   using C = G4<BN, WM, WN, STAGES>;
   const int64_t units = ((d.M + G4_BM - 1) / G4_BM) * ((d.N + BN - 1) / BN) * p.split;
   const dim3 grid((unsigned)persistent_grid(units));
-  if (d.a_mode == VD_A_CONV3X3)
+  if (d.a_mode == VD_A_CONV3X3 && p.pad_end)
+    hipLaunchKernelGGL((gemm4_kernel<BN, WM, WN, STAGES, A_CONV_PAD_END>), grid, dim3(C::NT), 0, s, d, p.a0b, p.a1b,
+                       p.wb, p.split);
+  else if (d.a_mode == VD_A_CONV3X3)
     hipLaunchKernelGGL((gemm4_kernel<BN, WM, WN, STAGES, VD_A_CONV3X3>), grid, dim3(C::NT), 0, s, d, p.a0b, p.a1b,
                        p.wb, p.split);
   else if (d.ln_out)  // the plan only lets a fusable descriptor keep ln_out

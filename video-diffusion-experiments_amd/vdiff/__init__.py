@@ -8,9 +8,11 @@ from .config import FULL, TINY, get_config  # noqa: F401
 from .models import UNetMotionModel, UNetMotionOutput  # noqa: F401
 from .models.clip import CLIPTextModel, CLIPTextModelOutput  # noqa: F401
 from .models.dit import DiT3DModel, DiTDenoiseLoop, DiTOutput  # noqa: F401
-from .models.vae import AutoencoderKL, DecoderOutput  # noqa: F401
+from .models.vae import (AutoencoderKL, AutoencoderKLOutput, DecoderOutput,  # noqa: F401
+                         DiagonalGaussianDistribution)
 from .pretrained import MotionAdapter  # noqa: F401
-from .pipeline import AnimateDiffPipeline, AnimateDiffPipelineOutput, DenoiseLoop  # noqa: F401
+from .pipeline import (AnimateDiffPipeline, AnimateDiffPipelineOutput,  # noqa: F401
+                       AnimateDiffVideoToVideoPipeline, DenoiseLoop)
 from .sched import (DDIMScheduler, DDIMSchedulerOutput, EulerDiscreteScheduler,  # noqa: F401
                     EulerDiscreteSchedulerOutput)
 from .tokenizer import CLIPTokenizer  # noqa: F401

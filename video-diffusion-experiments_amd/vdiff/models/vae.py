@@ -1,11 +1,15 @@
-"""AutoencoderKL decoder — the VAE decode of `diffusers:AnimateDiffPipeline.decode_latents`
+"""AutoencoderKL — the VAE decode of `diffusers:AnimateDiffPipeline.decode_latents`
 (SURVEY.md §8f rank 1): SD-1.5's `vae` as the reference loads it with the pipeline
 (experiments/05_grid_search_ablation.py:130-134) and slices it per frame
 (`pipe.enable_vae_slicing()`, :143).  Module tree and parameter names are diffusers'
 (`post_quant_conv`, `decoder.conv_in`, `decoder.mid_block.{resnets,attentions}`,
 `decoder.up_blocks[i].{resnets,upsamplers}`, `decoder.conv_norm_out`, `decoder.conv_out`),
-so diffusers-keyed safetensors load with vdiff.load_diffusers_state_dict; the encoder
-(`quant_conv`, `encoder.*`) is not on the text-to-video path and is not built.
+so diffusers-keyed safetensors load with vdiff.load_diffusers_state_dict.  The encoder
+(`encoder.conv_in`, `encoder.down_blocks[i].{resnets,downsamplers}`, `encoder.mid_block`,
+`encoder.conv_norm_out`, `encoder.conv_out`, `quant_conv`) is not on the text-to-video path:
+it is built only by `AutoencoderKL(config, encoder=True)` (the video-to-video pipeline's
+`encode(x).latent_dist`), registered after the decoder so the decoder's synthetic weights
+(init_synthetic_ draws in named_parameters() order) are the same with and without it.
 
 MI355X layout: frames are decoded in chunks of `frames_per_chunk` (default 8: one
 chunk's 512x512x256 activation is 1 GiB, inside the GEMM's 32-bit buffer offsets; the
@@ -18,7 +22,10 @@ bf16 rows over (frame, y, x), and each op is a vdiff kernel:
     (softmax scale * log2 e folded into q's weight and bias), then ONE flash pass over every
     frame (vd_attention with d = 512 -> flash512_kernel, csrc/attention_d512.hip: no score
     matrix in memory; round 2 materialised a 64 MB fp32 S per frame and ran GEMM ->
-    vd_softmax_rows -> GEMM), out = O.W_o^T + b_o + x.
+    vd_softmax_rows -> GEMM), out = O.W_o^T + b_o + x;
+  * the encoder's Downsample2D(padding=0) — F.pad(x, (0, 1, 0, 1)) then a stride-2 conv
+    without padding — is the conv loaders' pad-end mode (VD_CONV_PAD_END): no padded copy.
+Encoding runs in the same chunks: 8 frames' 512x512x128 activation is 0.5 GiB.
 """
 from __future__ import annotations
 
@@ -34,6 +41,7 @@ from .. import ops
 from .layers import Act, bf, f32, pack_conv3x3
 
 DecoderOutput = namedtuple("DecoderOutput", ["sample"])
+AutoencoderKLOutput = namedtuple("AutoencoderKLOutput", ["latent_dist"])
 
 VAE_FULL = dict(  # SD-1.5 vae/config.json
     in_channels=3,
@@ -197,15 +205,121 @@ class Decoder(nn.Module):
         return out, x.h, x.w
 
 
-class AutoencoderKL(nn.Module):
-    """Decode side of diffusers:AutoencoderKL: `decode(z).sample`, `.config`, `.dtype`, `.device`."""
+class Downsample2D(nn.Module):
+    """diffusers:Downsample2D(use_conv=True, padding=0) as the VAE encoder builds it:
+    F.pad(x, (0, 1, 0, 1)) then conv(3x3, stride 2, padding 0)."""
 
-    def __init__(self, config="full"):
+    def __init__(self, channels):
+        super().__init__()
+        self.conv = nn.Conv2d(channels, channels, 3, stride=2, padding=0)
+
+    def prepare(self):
+        self._w, self._b = pack_conv3x3(self.conv.weight), f32(self.conv.bias)
+
+    def forward(self, x: Act) -> Act:
+        t, h, w = ops.conv3x3(x.t, x.n, x.h, x.w, self._w, stride=2, pad_end=True, bias=self._b)
+        return Act(t, x.n, h, w)
+
+
+class DownEncoderBlock2D(nn.Module):
+    def __init__(self, in_channels, out_channels, num_layers, add_downsample, groups=32):
+        super().__init__()
+        self.resnets = nn.ModuleList([VAEResnetBlock2D(in_channels if i == 0 else out_channels, out_channels,
+                                                       groups) for i in range(num_layers)])
+        self.downsamplers = nn.ModuleList([Downsample2D(out_channels)]) if add_downsample else None
+
+    def forward(self, x: Act) -> Act:
+        for r in self.resnets:
+            x = r(x)
+        if self.downsamplers is not None:
+            x = self.downsamplers[0](x)
+        return x
+
+
+class Encoder(nn.Module):
+    """diffusers:Encoder(double_z=True): conv_in, DownEncoderBlock2D per block_out_channels entry
+    (layers_per_block resnets, a downsampler on all but the last), UNetMidBlock2D, GroupNorm +
+    SiLU, conv_out to 2 * latent_channels (mean | logvar)."""
+
+    def __init__(self, cfg):
+        super().__init__()
+        ch = list(cfg["block_out_channels"])
+        g = cfg["norm_num_groups"]
+        self.groups = g
+        self.conv_in = nn.Conv2d(cfg["in_channels"], ch[0], 3, padding=1)
+        blocks, prev = [], ch[0]
+        for i, c in enumerate(ch):
+            blocks.append(DownEncoderBlock2D(prev, c, cfg["layers_per_block"], i < len(ch) - 1, g))
+            prev = c
+        self.down_blocks = nn.ModuleList(blocks)
+        self.mid_block = UNetMidBlock2D(ch[-1], g)
+        self.conv_norm_out = nn.GroupNorm(g, ch[-1], eps=1e-6, affine=True)
+        self.conv_act = nn.SiLU()
+        self.conv_out = nn.Conv2d(ch[-1], 2 * cfg["latent_channels"], 3, padding=1)
+
+    def prepare(self):
+        self._gn, self._bn = f32(self.conv_norm_out.weight), f32(self.conv_norm_out.bias)
+        # RGB rows are packed to 8 channels (16-byte chunks), as the decoder's latent rows
+        self._w_in, self._b_in = pack_conv3x3(self.conv_in.weight, cin_pad=8), f32(self.conv_in.bias)
+        self._w_out, self._b_out = pack_conv3x3(self.conv_out.weight), f32(self.conv_out.bias)
+
+    def forward(self, x: Act) -> Act:
+        t, _, _ = ops.conv3x3(x.t, x.n, x.h, x.w, self._w_in, bias=self._b_in)
+        x = Act(t, x.n, x.h, x.w)
+        for blk in self.down_blocks:
+            x = blk(x)
+        x = self.mid_block(x)
+        h = ops.group_norm(x.t, x.n, x.h * x.w, self.groups, 1e-6, self._gn, self._bn, silu=True)
+        out, _, _ = ops.conv3x3(h, x.n, x.h, x.w, self._w_out, bias=self._b_out)
+        return Act(out, x.n, x.h, x.w)
+
+
+class DiagonalGaussianDistribution:
+    """diffusers:DiagonalGaussianDistribution over the encoder's moments (N, 2C, h, w) = mean |
+    logvar, logvar clamped to [-30, 20].  The posterior arithmetic is elementwise over the latents,
+    once per video: plain torch."""
+
+    def __init__(self, parameters: torch.Tensor, deterministic: bool = False):
+        self.parameters = parameters
+        self.mean, self.logvar = torch.chunk(parameters, 2, dim=1)
+        self.logvar = torch.clamp(self.logvar, -30.0, 20.0)
+        self.deterministic = deterministic
+        self.std = torch.exp(0.5 * self.logvar)
+        self.var = torch.exp(self.logvar)
+        if deterministic:
+            self.var = self.std = torch.zeros_like(self.mean)
+
+    def sample(self, generator=None) -> torch.Tensor:
+        from ..pipeline import randn_tensor
+        noise = randn_tensor(self.mean.shape, generator=generator, device=self.parameters.device,
+                             dtype=self.parameters.dtype)
+        return self.mean + self.std * noise
+
+    def kl(self, other=None) -> torch.Tensor:
+        if self.deterministic:
+            return torch.zeros(self.mean.shape[0], device=self.mean.device, dtype=self.mean.dtype)
+        if other is None:
+            return 0.5 * torch.sum(torch.pow(self.mean, 2) + self.var - 1.0 - self.logvar, dim=[1, 2, 3])
+        return 0.5 * torch.sum(torch.pow(self.mean - other.mean, 2) / other.var + self.var / other.var - 1.0
+                               - self.logvar + other.logvar, dim=[1, 2, 3])
+
+    def mode(self) -> torch.Tensor:
+        return self.mean
+
+
+class AutoencoderKL(nn.Module):
+    """diffusers:AutoencoderKL: `decode(z).sample`, `.config`, `.dtype`, `.device`, and — built with
+    encoder=True — `encode(x).latent_dist`."""
+
+    def __init__(self, config="full", encoder=False):
         super().__init__()
         cfg = copy.deepcopy(VAE_CONFIGS[config] if isinstance(config, str) else dict(config))
         self.config = cfg
         self.post_quant_conv = nn.Conv2d(cfg["latent_channels"], cfg["latent_channels"], 1)
         self.decoder = Decoder(cfg)
+        # after the decoder: the synthetic weight stream of the modules above does not move
+        self.encoder = Encoder(cfg) if encoder else None
+        self.quant_conv = nn.Conv2d(2 * cfg["latent_channels"], 2 * cfg["latent_channels"], 1) if encoder else None
         self.frames_per_chunk = 8
         self._prepared = False
 
@@ -234,6 +348,10 @@ class AutoencoderKL(nn.Module):
         d = self.decoder
         d._w_in = pack_conv3x3(d.conv_in.weight, cin_pad=8)
         d._b_in = f32(d.conv_in.bias)
+        if self.encoder is not None:
+            mc = 2 * lc
+            self._w_q = bf(self.quant_conv.weight.reshape(mc, mc))
+            self._b_q = f32(self.quant_conv.bias)
         self._prepared = True
         return self
 
@@ -258,3 +376,35 @@ class AutoencoderKL(nn.Module):
             outs.append(ops.unpack_nhwc(out, 1, self.decoder._cout, n, H, W)[0].permute(1, 0, 2, 3))
         img = torch.cat(outs, 0)
         return DecoderOutput(img) if return_dict else (img,)
+
+    def encode_rows(self, x_rows, n, H, W):
+        """Packed RGB rows [n*H*W, 8] (channels >= 3 zero) -> fp32 moment rows
+        [n*h*w, 2*latent_channels] (mean | logvar) and (h, w)."""
+        e = self.encoder(Act(x_rows, n, H, W))
+        return ops.gemm(e.t, self._w_q, bias=self._b_q, out_f32=True), e.h, e.w  # quant_conv (1x1)
+
+    @torch.no_grad()
+    def encode(self, x: torch.Tensor, return_dict: bool = True):
+        """x (N, 3, H, W) in [-1, 1], H and W multiples of 8 -> AutoencoderKLOutput(latent_dist=
+        DiagonalGaussianDistribution over fp32 moments (N, 2*latent_channels, H/s, W/s)), s = 2 per
+        downsampler (8 for SD-1.5).  Frames go through in chunks of frames_per_chunk."""
+        if self.encoder is None:
+            raise ValueError("this AutoencoderKL was built without its encoder: AutoencoderKL(config, encoder=True) "
+                             "(load_vae builds it when the checkpoint holds the whole encoder)")
+        if x.dim() != 4 or x.shape[1] != self.config["in_channels"]:
+            raise ValueError(f"encode takes (N, {self.config['in_channels']}, H, W), got {tuple(x.shape)}")
+        N, C, H, W = x.shape
+        if H % 8 or W % 8:
+            raise ValueError(f"encode: height and width must be multiples of 8, got {H} x {W}")
+        if not self._prepared:
+            self.prepare()
+        mc = 2 * self.config["latent_channels"]
+        outs = []
+        for i in range(0, N, self.frames_per_chunk):
+            xc = x[i:i + self.frames_per_chunk].to(self.device, torch.float32)
+            n = xc.shape[0]
+            rows = ops.pack_latents(xc.permute(1, 0, 2, 3)[None].contiguous(), dup=1, cpad=8)
+            mom, h, w = self.encode_rows(rows, n, H, W)
+            outs.append(ops.unpack_nhwc(mom, 1, mc, n, h, w)[0].permute(1, 0, 2, 3))
+        dist = DiagonalGaussianDistribution(torch.cat(outs, 0).contiguous())
+        return AutoencoderKLOutput(dist) if return_dict else (dist,)

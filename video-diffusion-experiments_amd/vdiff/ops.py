@@ -16,6 +16,7 @@ from ._lib import VD_EUNSUPPORTED, GemmDesc, check, lib
 
 ACT_NONE, ACT_SILU, ACT_GEGLU, ACT_GELU, ACT_QUICK_GELU = 0, 1, 2, 3, 4
 A_DENSE, A_CONV3X3 = 0, 1
+CONV_PAD_END = 0x100  # VD_CONV_PAD_END, OR-ed into vd_gemm_desc.stride
 BF16 = torch.bfloat16
 
 
@@ -269,16 +270,23 @@ def ff_fused(x, w1, w2, *, b1=None, b2=None, res=None, ln_fold=None, out=None):
     return out
 
 
-def conv3x3(x, n_img, h_in, w_in, w, *, x1=None, stride=1, upsample=False, bias=None,
+def conv3x3(x, n_img, h_in, w_in, w, *, x1=None, stride=1, upsample=False, pad_end=False, bias=None,
             rowbias=None, rb_div=1, res=None, act=ACT_NONE, out=None, out_f32=False):
-    """3x3 pad-1 conv over NHWC rows x (+ channel-concat x1); w packed [Cout][3][3][Cin]."""
+    """3x3 pad-1 conv over NHWC rows x (+ channel-concat x1); w packed [Cout][3][3][Cin].
+    pad_end (stride 2 only): the VAE encoder's Downsample2D(padding=0) instead —
+    conv2d(F.pad(x, (0, 1, 0, 1)), w, stride=2), zeros past the far edges only
+    (VD_CONV_PAD_END), output (h_in - 2) // 2 + 1 by (w_in - 2) // 2 + 1."""
     _dev(x, w, x1, bias, rowbias, res, out)
     N, K = w.shape
     c0 = x.shape[1]
     if K % 9 or (c0 + (x1.shape[1] if x1 is not None else 0)) * 9 != K:
         raise ValueError("conv weight K does not match input channels")
+    if pad_end and (stride != 2 or upsample or h_in < 2 or w_in < 2):
+        raise ValueError("pad_end is the stride-2 conv without upsample over at least 2 x 2 pixels")
     if upsample:
         h_out, w_out = 2 * h_in, 2 * w_in
+    elif pad_end:
+        h_out, w_out = (h_in - 2) // 2 + 1, (w_in - 2) // 2 + 1
     else:
         h_out, w_out = (h_in - 1) // stride + 1, (w_in - 1) // stride + 1
     M = n_img * h_out * w_out
@@ -287,7 +295,7 @@ def conv3x3(x, n_img, h_in, w_in, w, *, x1=None, stride=1, upsample=False, bias=
     d = GemmDesc(a0=_p(x), lda0=_rows(x), k0=c0, a1=_p(x1),
                  lda1=_rows(x1) if x1 is not None else 0, a_mode=A_CONV3X3,
                  n_img=n_img, h_in=h_in, w_in=w_in, h_out=h_out, w_out=w_out,
-                 stride=stride, upsample=int(bool(upsample)),
+                 stride=stride | (CONV_PAD_END if pad_end else 0), upsample=int(bool(upsample)),
                  w=_p(w), ldw=_rows(w), M=M, N=N, K=K)
     out = _set_epilogue(d, M, x.device, bias=bias, rowbias=rowbias, rb_div=rb_div, res=res, act=act, out=out,
                         out_f32=out_f32)

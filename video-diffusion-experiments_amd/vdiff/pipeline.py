@@ -35,6 +35,10 @@ drawn on the generator's device — the CPU for 05:156's `torch.manual_seed(seed
 for 01:103's `torch.Generator("cuda").manual_seed(seed)` — in the pipeline's torch_dtype
 (float16 in the reference, 05:35, 05:130-134), then moved to the GPU (kept in fp32 from
 there on).
+
+AnimateDiffVideoToVideoPipeline (diffusers' second AnimateDiff pipeline) starts the same loop
+from a video: the frames are encoded by the VAE encoder (`AutoencoderKL(..., encoder=True)`),
+noised to the timestep `strength` picks, and denoised over the remaining timesteps.
 """
 from __future__ import annotations
 
@@ -222,6 +226,7 @@ class AnimateDiffPipeline:
     # pipeline with torch_dtype=torch.float16 (05:35, 05:130-134) and diffusers' randn_tensor
     # draws in that dtype
     latent_draw_dtype = torch.float16
+    vae_encoder = False  # from_config's synthetic VAE: decoder only (text-to-video never encodes)
 
     def __init__(self, unet: UNetMotionModel, scheduler=None, text_encoder=None, vae=None, dist=None,
                  tokenizer=None):
@@ -252,7 +257,7 @@ class AnimateDiffPipeline:
         sched = scheduler or DDIMScheduler.from_config(None, beta_schedule="linear", steps_offset=1,
                                                        clip_sample=False)
         if isinstance(vae, str):
-            vae = init_synthetic_(AutoencoderKL(vae), seed).to(device=device, dtype=torch.bfloat16).prepare()
+            vae = init_synthetic_(AutoencoderKL(vae, encoder=cls.vae_encoder), seed).to(device=device, dtype=torch.bfloat16).prepare()
         pipe = cls(unet, sched, dist=dist, vae=vae)
         pipe.torch_dtype = cls.latent_draw_dtype  # the reference's torch_dtype=torch.float16 (05:35)
         return pipe
@@ -399,6 +404,151 @@ class AnimateDiffPipeline:
             fl = self.dist.frames_local(num_frames)
             local = latents[:, :, self.dist.rank * fl:(self.dist.rank + 1) * fl]
         loop = DenoiseLoop(self.unet, self.scheduler, local, ehs, guidance_scale,
+                           use_graph=use_graph).prime()
+        out = loop.run()
+        if self.dist is not None:
+            out = self.dist.all_gather_frames(out)
+        if output_type != "latent":
+            out = self.postprocess_video(self.decode_latents(out), output_type)
+        return AnimateDiffPipelineOutput(frames=out) if return_dict else (out,)
+
+
+def preprocess_video(video, height=None, width=None):
+    """The video-to-video input -> (B, 3, F, H, W) fp32 in [-1, 1] on the CPU.  Accepted: a list of
+    PIL frames or a list of such lists; an ndarray (F, H, W, 3) or (B, F, H, W, 3) in [0, 1]; a
+    tensor (F, 3, H, W) or (B, F, 3, H, W) in [0, 1].  height / width default to the video's own
+    size.  PIL frames of another size are resized (LANCZOS); arrays and tensors are refused."""
+    import numpy as np
+    if isinstance(video, (list, tuple)) and len(video) > 0 and not torch.is_tensor(video[0]) \
+            and not isinstance(video[0], np.ndarray):
+        from PIL import Image
+        vids = [list(video)] if isinstance(video[0], Image.Image) else [list(v) for v in video]
+        if not all(len(v) > 0 and all(isinstance(f, Image.Image) for f in v) for v in vids):
+            raise ValueError("video: a list of PIL frames, or a list of such lists")
+        if len({len(v) for v in vids}) != 1:
+            raise ValueError("video: every video of the batch needs the same number of frames")
+        w0, h0 = vids[0][0].size
+        height, width = height or h0, width or w0
+        arr = np.stack([np.stack([np.asarray((f if f.size == (width, height)
+                                              else f.resize((width, height), Image.LANCZOS)).convert("RGB"),
+                                             dtype=np.float32) / 255.0 for f in v]) for v in vids])
+        x = torch.from_numpy(arr).permute(0, 1, 4, 2, 3)              # (B, F, 3, H, W)
+    elif isinstance(video, np.ndarray):
+        if video.ndim not in (4, 5) or video.shape[-1] != 3:
+            raise ValueError(f"video array: (F, H, W, 3) or (B, F, H, W, 3), got {video.shape}")
+        x = torch.from_numpy(np.ascontiguousarray(video)).float()
+        x = (x[None] if x.dim() == 4 else x).permute(0, 1, 4, 2, 3)
+    elif torch.is_tensor(video):
+        if video.dim() not in (4, 5) or video.shape[-3] != 3:
+            raise ValueError(f"video tensor: (F, 3, H, W) or (B, F, 3, H, W), got {tuple(video.shape)}")
+        x = video.detach().float().cpu()
+        x = x[None] if x.dim() == 4 else x
+    else:
+        raise ValueError("video: PIL frames, an ndarray or a tensor")
+    H, W = x.shape[-2:]
+    if (height or H) != H or (width or W) != W:
+        raise ValueError(f"video is {H} x {W}, asked for {height} x {width}: only PIL frames are resized")
+    if H % 8 or W % 8:
+        raise ValueError(f"video height and width must be multiples of 8, got {H} x {W}")
+    return (2.0 * x - 1.0).permute(0, 2, 1, 3, 4).contiguous()
+
+
+class AnimateDiffVideoToVideoPipeline(AnimateDiffPipeline):
+    """diffusers AnimateDiffVideoToVideoPipeline: `pipe(video=, prompt=, strength=, ...)` encodes
+    the video, noises it to the timestep `strength` picks and runs the text-to-video pipeline's
+    denoising loop (the same captured graph) over the remaining timesteps.  Parity to diffusers
+    is unpinned, as the decoder's."""
+
+    vae_encoder = True
+
+    def __init__(self, unet, scheduler=None, text_encoder=None, vae=None, dist=None, tokenizer=None):
+        super().__init__(unet, scheduler, text_encoder=text_encoder, vae=vae, dist=dist, tokenizer=tokenizer)
+        if vae is None or getattr(vae, "encoder", None) is None:
+            raise ValueError("AnimateDiffVideoToVideoPipeline needs a VAE with its encoder: "
+                             "AutoencoderKL(config, encoder=True), or a vae/ checkpoint that holds every "
+                             "encoder.* and quant_conv.* tensor")
+
+    def get_timesteps(self, num_inference_steps, strength):
+        """diffusers get_timesteps: the last min(int(n * strength), n) timesteps of the schedule
+        (set_timesteps first) and their count."""
+        if not 0.0 < strength <= 1.0:
+            raise ValueError(f"strength must be in (0, 1], got {strength}")
+        init = min(int(num_inference_steps * strength), num_inference_steps)
+        if init == 0:
+            raise ValueError(f"strength {strength} with {num_inference_steps} steps leaves no step to run")
+        t_start = max(num_inference_steps - init, 0)
+        ts = self.scheduler.timesteps[t_start * self.scheduler.order:]
+        return ts, num_inference_steps - t_start
+
+    @torch.no_grad()
+    def encode_video(self, video, generator=None):
+        """One video (F, 3, H, W) in [-1, 1] -> (F, C, h, w) latents x scaling_factor: chunks of
+        vae.frames_per_chunk frames, each chunk's posterior sampled with `generator` in turn."""
+        n = self.vae.frames_per_chunk
+        lat = [self.vae.encode(video[i:i + n]).latent_dist.sample(generator=generator)
+               for i in range(0, video.shape[0], n)]
+        return self.vae.config["scaling_factor"] * torch.cat(lat)
+
+    @torch.no_grad()
+    def prepare_latents(self, video, timestep, generator=None, latents=None):
+        """diffusers AnimateDiffVideoToVideoPipeline.prepare_latents -> (B, C, F, h, w) fp32 on the
+        GPU.  video (B, 3, F, H, W) in [-1, 1]; `latents` given bypasses encoding and noising.
+        Draw order on `generator` (one stream, as diffusers):
+          1. per video, per chunk of vae.frames_per_chunk frames in order: the posterior's
+             randn (chunk frames, C, h, w), drawn in fp32 (the moments' dtype here);
+          2. the latents x scaling_factor, stacked to (B, F, C, h, w);
+          3. ONE noise tensor (B, F, C, h, w) in the pipeline's torch_dtype (fp32 when None);
+          4. scheduler.add_noise(latents, noise, timestep);
+          5. permute to (B, C, F, h, w)."""
+        dev = self.unet.device
+        if latents is not None:
+            return latents.to(dev, torch.float32)
+        frames = video.permute(0, 2, 1, 3, 4)                             # (B, F, 3, H, W)
+        init = torch.stack([self.encode_video(v, generator) for v in frames]).to(dev, torch.float32)
+        noise = randn_tensor(init.shape, generator=generator, device=dev, dtype=self.torch_dtype or torch.float32)
+        x = self.scheduler.add_noise(init, noise.float(), torch.as_tensor(timestep).reshape(-1)[:1])
+        return x.permute(0, 2, 1, 3, 4).contiguous()
+
+    @torch.no_grad()
+    def __call__(self, video=None, prompt=None, negative_prompt=None, height=None, width=None,
+                 num_inference_steps=50, guidance_scale=7.5, strength=0.8, num_videos_per_prompt=1, eta=0.0,
+                 generator=None, latents=None, prompt_embeds=None, negative_prompt_embeds=None,
+                 output_type="pil", return_dict=True, clip_skip=None, use_graph=True, **unused):
+        if eta != 0.0:
+            raise NotImplementedError("eta > 0")
+        if output_type not in ("latent", "pt", "np", "pil"):
+            raise NotImplementedError(f"output_type {output_type!r}: use 'pil', 'pt', 'np' or 'latent'")
+        if video is None and latents is None:
+            raise ValueError("video or latents required")
+        do_cfg = guidance_scale > 1
+        if prompt_embeds is None:
+            if prompt is None:
+                raise ValueError("prompt or prompt_embeds required")
+            pos = [prompt] if isinstance(prompt, str) else list(prompt)
+            prompt_embeds = self.encode_prompt(pos, len(pos), clip_skip=clip_skip)
+        B = prompt_embeds.shape[0] * num_videos_per_prompt
+        prompt_embeds = prompt_embeds.repeat_interleave(num_videos_per_prompt, 0)
+        if do_cfg:
+            if negative_prompt_embeds is None:
+                negative_prompt_embeds = self.encode_prompt(negative_prompt or "", B, clip_skip=clip_skip)
+            ehs = torch.cat([negative_prompt_embeds.to(prompt_embeds), prompt_embeds])
+        else:
+            ehs = prompt_embeds
+        self.scheduler.set_timesteps(num_inference_steps)
+        ts, _ = self.get_timesteps(num_inference_steps, strength)
+        if latents is None:
+            video = preprocess_video(video, height, width)
+            if video.shape[0] == 1 and B > 1:
+                video = video.expand(B, -1, -1, -1, -1)
+            if video.shape[0] != B:
+                raise ValueError(f"{video.shape[0]} videos for a batch of {B}")
+        latents = self.prepare_latents(video, ts[:1], generator=generator, latents=latents)
+        num_frames = latents.shape[2]
+        local = latents
+        if self.dist is not None:  # every rank computed the same latents from the shared CPU generator
+            fl = self.dist.frames_local(num_frames)
+            local = latents[:, :, self.dist.rank * fl:(self.dist.rank + 1) * fl]
+        loop = DenoiseLoop(self.unet, self.scheduler, local, ehs, guidance_scale, timesteps=ts,
                            use_graph=use_graph).prime()
         out = loop.run()
         if self.dist is not None:

@@ -14,7 +14,9 @@ UNet2DConditionModel keys and the adapter the `*.motion_modules.*` keys; diffuse
 UNetMotionModel.from_unet2d joins the two under exactly those names, which are the names of
 vdiff.UNetMotionModel's parameters, so the join is a dict union.  The adapter's
 `pos_embed.pe` buffers are recomputed (they are fixed sinusoids).  The VAE's encoder half
-(`encoder.*`, `quant_conv.*`) is not on the text-to-video path and is skipped.  Weights are
+(`encoder.*`, `quant_conv.*`) is not on the text-to-video path: it is built when the checkpoint
+holds every one of its tensors (the video-to-video pipeline needs it) and skipped otherwise.
+Weights are
 stored in bf16 on the device: the kernels compute in bf16, whatever `torch_dtype` the caller
 passes (the reference's float16 is recorded in `.torch_dtype`).
 """
@@ -134,11 +136,11 @@ def vae_config(cfg: dict) -> dict:
     return out
 
 
-def _empty_on(cls, cfg, device):
+def _empty_on(cls, cfg, device, **kw):
     """Build on the meta device, then allocate on `device` (no fp32 CPU copy of 1.3B params)."""
     from .models.layers import SinusoidalPositionalEmbedding
     with torch.device("meta"):
-        m = cls(cfg)
+        m = cls(cfg, **kw)
     m = m.to_empty(device=device)
     for mod in m.modules():
         if isinstance(mod, SinusoidalPositionalEmbedding):
@@ -177,9 +179,16 @@ def load_unet_motion(unet_dir, adapter: MotionAdapter, device="cuda", variant=No
 def load_vae(vae_dir, device="cuda", variant=None):
     from .models.vae import AutoencoderKL
     d = _local_dir(vae_dir, "vae")
-    vae = _empty_on(AutoencoderKL, vae_config(read_json(d / "config.json")), device)
-    return _assign(vae, load_weights(d, variant), skip=lambda k: k.startswith(("encoder.", "quant_conv.")),
-                   what="AutoencoderKL")
+    cfg = vae_config(read_json(d / "config.json"))
+    sd = load_weights(d, variant)
+    # the encoder is built only from a checkpoint that holds all of it; a partial one (or none) gives
+    # the decoder-only model, whose encode() says so
+    enc = ("encoder.", "quant_conv.")
+    with torch.device("meta"):
+        want = {k for k in AutoencoderKL(cfg, encoder=True).state_dict() if k.startswith(enc)}
+    whole = want <= set(sd)
+    vae = _empty_on(AutoencoderKL, cfg, device, encoder=whole)
+    return _assign(vae, sd, skip=(lambda k: False) if whole else (lambda k: k.startswith(enc)), what="AutoencoderKL")
 
 
 def load_text_encoder(enc_dir, device="cuda", variant=None):

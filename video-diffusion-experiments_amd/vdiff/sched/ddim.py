@@ -135,6 +135,17 @@ class DDIMScheduler:
         ts = self.timesteps if timesteps is None else timesteps
         return torch.stack([self.coefficients(t) for t in ts.tolist()])
 
+    def add_noise(self, original_samples, noise, timesteps):
+        """diffusers DDIMScheduler.add_noise: sqrt(a_t) * x + sqrt(1 - a_t) * noise in fp32 torch
+        math, in that order; `timesteps` a scalar or one per batch row (the video-to-video
+        pipeline noises the encoded video at its first timestep).  Square roots as `coefficients`."""
+        t = torch.as_tensor(timesteps).reshape(-1).long().cpu()
+        x = original_samples.float()
+        shape = (-1,) + (1,) * (x.dim() - 1)
+        sa = sqrt32(self.alphas_cumprod[t]).to(x.device).reshape(shape)
+        sb = sqrt32(1 - self.alphas_cumprod[t]).to(x.device).reshape(shape)
+        return sa * x + sb * noise.to(x.device, torch.float32)
+
     def step(self, model_output, timestep, sample, eta: float = 0.0, use_clipped_model_output=False,
              generator=None, variance_noise=None, return_dict: bool = True):
         if self.num_inference_steps is None:

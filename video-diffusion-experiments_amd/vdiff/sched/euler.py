@@ -157,6 +157,16 @@ class EulerDiscreteScheduler:
         pos = {float(t): i for i, t in enumerate(self.timesteps.cpu().tolist())}
         return torch.stack([self.coefficients(pos[float(t)]) for t in ts.cpu().tolist()])
 
+    def add_noise(self, original_samples, noise, timesteps):
+        """diffusers EulerDiscreteScheduler.add_noise: x + noise * sigma_t in fp32, sigma at
+        index_for_timestep(t) of the current schedule (set_timesteps first); `timesteps` a scalar
+        or one per batch row."""
+        x = original_samples.float()
+        t = torch.as_tensor(timesteps).reshape(-1).cpu()
+        idx = [self.index_for_timestep(v) for v in t.tolist()]
+        sigma = self.sigmas[idx].to(x.device).reshape((-1,) + (1,) * (x.dim() - 1))
+        return x + noise.to(x.device, torch.float32) * sigma
+
     def step(self, model_output, timestep, sample, s_churn: float = 0.0, s_tmin: float = 0.0,
              s_tmax: float = float("inf"), s_noise: float = 1.0, generator=None, return_dict: bool = True):
         if self.num_inference_steps is None:
