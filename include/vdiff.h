@@ -293,8 +293,20 @@ int vd_attention_f32(const void* q, int64_t ldq, const void* k, int64_t ldk, con
  * self-attention).  It needs sq == skv and kv_div == 1 (else VD_EINVAL), scale > 0 (else
  * VD_EINVAL) and d in {32, 64} (else VD_EUNSUPPORTED); it always runs the 16x16x32 flash kernel,
  * whose causal instances skip the key tiles wholly above the diagonal.  Any other bit above the
- * low byte is VD_EINVAL.  vd_attention and vd_attention_f32 are never causal. */
+ * low byte is VD_EINVAL.  vd_attention and vd_attention_f32 are never causal.
+ * VD_ATTN_TAIL(n) OR-ed into kernel, 1 <= n <= 64: two-segment attention (the IP-Adapter image
+ * prompt).  Of the skv K/V rows of a key batch, rows [0, skv - n) are segment A (the text) and rows
+ * [skv - n, skv) are segment B (the image tokens); each segment has a softmax of its own and
+ *     o = softmax(q K_A^T scale) V_A + softmax(q K_B^T scale) V_B,
+ * summed in fp32 before the one store (an adapter scale is folded into V_B by the caller).
+ * kv_div, the row strides, out_f32 and the batch layout (k + bkv*skv*ldk) are those of an
+ * untailed call.  It needs n < skv, no VD_ATTN_CAUSAL and scale > 0 (else VD_EINVAL; n > 64 does
+ * not fit the mask) and d in {32, 40, 64, 80, 160} (else VD_EUNSUPPORTED); it always runs the
+ * 16x16x32 flash kernel whatever the low byte says.  With V_B = 0 the result is bit-identical to
+ * kernel = 1 on segment A alone.  vd_attention and vd_attention_f32 never take a tail. */
 enum { VD_ATTN_CAUSAL = 0x100 };
+enum { VD_ATTN_TAIL_SHIFT = 16, VD_ATTN_TAIL_MASK = 0x7f0000 };
+#define VD_ATTN_TAIL(n) ((n) << VD_ATTN_TAIL_SHIFT)
 int vd_attention_ex(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
                     void* o, int64_t ldo, int64_t batch, int32_t heads, int64_t sq, int64_t skv, int32_t d,
                     int64_t kv_div, float scale, int32_t out_f32, int32_t kernel, vd_stream_t stream);

@@ -61,14 +61,14 @@ __device__ __forceinline__ float max_over_query_lanes(float x) {
 template <int L>
 using stage_t = __attribute__((ext_vector_type(8 * L))) uint32_t;  // K chunks then V chunks
 
+// One tile of up to KT keys starting at row key0; rows past kmax (the tile's last valid row) are
+// clamped to it.
 template <int L>
-__device__ __forceinline__ stage_t<L> kv_load(const bf16_t* kb_ptr, const bf16_t* vb_ptr, int ldk,
-                                              int ldv, int t, int64_t skv, const int (&krow)[L],
-                                              const uint32_t (&kcol)[L]) {
-  const int64_t key0 = (int64_t)t * KT;
+__device__ __forceinline__ stage_t<L> kv_load_rows(const bf16_t* kb_ptr, const bf16_t* vb_ptr, int ldk,
+                                                   int ldv, int64_t key0, int kmax, const int (&krow)[L],
+                                                   const uint32_t (&kcol)[L]) {
   const bf16_t* kp = kb_ptr + key0 * ldk;
   const bf16_t* vp = vb_ptr + key0 * ldv;
-  const int kmax = (int)(skv - 1 - key0);  // >= KT-1 except on a ragged last tile
   stage_t<L> st;
 #pragma unroll
   for (int i = 0; i < L; ++i) {
@@ -80,6 +80,14 @@ __device__ __forceinline__ stage_t<L> kv_load(const bf16_t* kb_ptr, const bf16_t
     st[4 * L + 4 * i + 2] = b.z; st[4 * L + 4 * i + 3] = b.w;
   }
   return st;
+}
+template <int L>
+__device__ __forceinline__ stage_t<L> kv_load(const bf16_t* kb_ptr, const bf16_t* vb_ptr, int ldk,
+                                              int ldv, int t, int64_t skv, const int (&krow)[L],
+                                              const uint32_t (&kcol)[L]) {
+  const int64_t key0 = (int64_t)t * KT;
+  // kmax >= KT-1 except on a ragged last tile
+  return kv_load_rows<L>(kb_ptr, vb_ptr, ldk, ldv, key0, (int)(skv - 1 - key0), krow, kcol);
 }
 template <int L>
 __device__ __forceinline__ void kv_store(const stage_t<L>& st, bf16_t* kl, bf16_t* vl,
@@ -96,11 +104,25 @@ __device__ __forceinline__ void kv_store(const stage_t<L>& st, bf16_t* kl, bf16_
 // j <= i.  A workgroup stops at the key tile that holds its last query (tiles wholly above the
 // diagonal are never loaded; the bound is workgroup-uniform because staging is cooperative), and
 // a wave masks the scores with key > query on the tiles that cross its diagonal.
-template <int D, int QBLK, bool CAUSAL = false>
+//
+// TAIL (compile time; VD_ATTN_TAIL, the IP-Adapter image tokens): the last `tail` (1..KT) of the
+// skv K/V rows are a second segment with a softmax of its own,
+//     o = softmax(q K_A^T) V_A + softmax(q K_B^T) V_B,   A = rows [0, skv - tail), B = the rest.
+// Segment A runs the tile loop exactly as a call with skv - tail keys would (same tiles, same
+// ragged mask, same clamped rows), then the accumulator is normalised in place by A's row sum —
+// the epilogue's reciprocal and multiply, so with V_B = 0 the stored bits are those of the
+// untailed call.  Segment B is one more trip through the loop on a single key tile loaded from
+// row skv - tail (staged under A's last tile like any other): its softmax is exact in one pass
+// (row max, p = exp2(s c - m), row sum across the query's 4 lanes, p / l packed to bf16) and its
+// PV MFMAs accumulate onto the normalised A result in the same registers; the epilogue stores
+// without dividing.  The ones column (DV > D) is spent once A is normalised, so B's row sum is
+// always summed explicitly.
+template <int D, int QBLK, bool CAUSAL = false, bool TAIL = false>
 __global__ __launch_bounds__(NT, 2) void flash_attn_kernel(
     const bf16_t* __restrict__ q, int64_t ldq, const bf16_t* __restrict__ k, int64_t ldk,
     const bf16_t* __restrict__ v, int64_t ldv, bf16_t* __restrict__ o, int64_t ldo, int heads,
-    int64_t sq, int64_t skv, int64_t kv_div, float c, int out_f32 = 0) {
+    int64_t sq, int64_t skv, int64_t kv_div, float c, int out_f32 = 0, int tail = 0) {
+  static_assert(!(CAUSAL && TAIL), "a tailed call is never causal");
   using C = AttnCfg<D>;
   // When PV is padded (DV > D) column D of V is set to 1.0, so the PV MFMA also
   // produces the softmax row sum (no per-score adds).
@@ -172,22 +194,89 @@ __global__ __launch_bounds__(NT, 2) void flash_attn_kernel(
 #pragma unroll
   for (int qb = 0; qb < QBLK; ++qb) { mrow[qb] = -INFINITY; lrow[qb] = 0.f; }
 
-  int ntiles = (int)((skv + KT - 1) / KT);
+  const int64_t kend = TAIL ? skv - tail : skv;  // keys of the tile loop (segment A of a tailed call)
+  int ntiles = (int)((kend + KT - 1) / KT);
   if constexpr (CAUSAL) {  // stop at the tile of the workgroup's last query (blockIdx only: uniform)
     int64_t qlast = ((int64_t)blockIdx.x + 1) * (4 * QWV) - 1;
     if (qlast > sq - 1) qlast = sq - 1;
     const int nt = (int)(qlast / KT) + 1;
     if (nt < ntiles) ntiles = nt;
   }
-  const bool ragged = (skv % KT) != 0;
-  kvst = kv_load<C::LREG>(kb_ptr, vb_ptr, ldk32, ldv32, 0, skv, krow, kcol);
+  const bool ragged = (kend % KT) != 0;
+  kvst = kv_load<C::LREG>(kb_ptr, vb_ptr, ldk32, ldv32, 0, kend, krow, kcol);
   kv_store<C::LREG>(kvst, ks_lds[0], vs_lds[0], ldsk, ldsv);
   __syncthreads();
   const int qq = fr >> 2, pp = fr & 3;  // tr-read geometry: lane 4*qq+pp -> row qq, cols 4*pp..
 
+  // The two MFMA passes of a key tile for segment B's tile: the tile loop's own, restated.  The
+  // loop keeps them inline — calling these helpers from it moved the untailed instances'
+  // register allocation and schedule, 0.3 % of the flagship step in an A/B against the parent.
+  // ---- S^T = K . Q^T
+  auto qk_tile = [&](const bf16_t* kl, f32x4 (&s)[4][QBLK]) __attribute__((always_inline)) {
+#pragma unroll
+    for (int kb = 0; kb < 4; ++kb)
+#pragma unroll
+      for (int qb = 0; qb < QBLK; ++qb) s[kb][qb] = f32x4{0.f, 0.f, 0.f, 0.f};
+    {  // K fragments two ahead in a rolling window (round 2): hipcc otherwise read each one right
+       // before its QBLK MFMAs behind an lgkmcnt(0) — an exposed LDS latency per fragment
+      constexpr int NK = C::DQK / 32 * 4;  // fragment i = (dc, kb) = (i / 4, i % 4)
+      auto kfrag = [&](int i) { return *(const bf16x8*)(kl + ((i % 4) * 16 + fr) * C::KS + (i / 4) * 32 + 8 * fg); };
+      bf16x8 k0 = kfrag(0), k1 = kfrag(1);
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int i = 0; i < NK; ++i) {
+        bf16x8 kn = k1;
+        if (i + 2 < NK) kn = kfrag(i + 2);
+#pragma unroll
+        for (int qb = 0; qb < QBLK; ++qb)
+          s[i % 4][qb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(k0, qf[qb][i / 4], s[i % 4][qb], 0, 0, 0);
+        k0 = k1;
+        k1 = kn;
+      }
+#pragma unroll
+      for (int i = 0; i < NK; ++i) {
+        if (i + 2 < NK) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(0x008, QBLK, 0);
+      }
+    }
+  };
+  // ---- O^T += V^T . P^T
+  auto pv_tile = [&](const bf16_t* vl, const bf16x8 (&pf)[2][QBLK]) __attribute__((always_inline)) {
+    {  // V^T fragments two ahead in a rolling window, as K above (fragment j = (a, st) = (j / 2, j % 2))
+      constexpr int NV = C::DV / 16 * 2;
+      auto vfrag = [&](int j) {
+        const bf16_t* p0 = vl + (32 * (j % 2) + 4 * fg + qq) * C::VS + (j / 2) * 16 + 4 * pp;
+        const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((bf16x4 __attribute__((address_space(3)))*)(p0));
+        const bf16x4 hi =
+            __builtin_amdgcn_ds_read_tr16_b64_v4bf16((bf16x4 __attribute__((address_space(3)))*)(p0 + 16 * C::VS));
+        return bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+      };
+      bf16x8 v0 = vfrag(0), v1 = vfrag(1);
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int j = 0; j < NV; ++j) {
+        bf16x8 vn = v1;
+        if (j + 2 < NV) vn = vfrag(j + 2);
+#pragma unroll
+        for (int qb = 0; qb < QBLK; ++qb)
+          oacc[j / 2][qb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(v0, pf[j % 2][qb], oacc[j / 2][qb], 0, 0, 0);
+        v0 = v1;
+        v1 = vn;
+      }
+#pragma unroll
+      for (int j = 0; j < NV; ++j) {
+        if (j + 2 < NV) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
+        __builtin_amdgcn_sched_group_barrier(0x008, QBLK, 0);
+      }
+    }
+  };
+
   for (int t = 0; t < ntiles; ++t) {
     const int buf = t & 1;
-    if (t + 1 < ntiles) kvst = kv_load<C::LREG>(kb_ptr, vb_ptr, ldk32, ldv32, t + 1, skv, krow, kcol);
+    if (t + 1 < ntiles) kvst = kv_load<C::LREG>(kb_ptr, vb_ptr, ldk32, ldv32, t + 1, kend, krow, kcol);
+    if constexpr (TAIL) {  // segment B's one tile is staged under A's last, as every other tile is
+      if (t + 1 == ntiles) kvst = kv_load_rows<C::LREG>(kb_ptr, vb_ptr, ldk32, ldv32, kend, tail - 1, krow, kcol);
+    }
     const bf16_t* kl = ks_lds[buf];
     const bf16_t* vl = vs_lds[buf];
 
@@ -225,7 +314,7 @@ __global__ __launch_bounds__(NT, 2) void flash_attn_kernel(
       for (int kb = 0; kb < 4; ++kb)
 #pragma unroll
         for (int j = 0; j < 4; ++j)
-          if (kbase + kb * 16 + j >= skv) {
+          if (kbase + kb * 16 + j >= kend) {
 #pragma unroll
             for (int qb = 0; qb < QBLK; ++qb) s[kb][qb][j] = -INFINITY;
           }
@@ -321,23 +410,95 @@ __global__ __launch_bounds__(NT, 2) void flash_attn_kernel(
         __builtin_amdgcn_sched_group_barrier(0x008, QBLK, 0);
       }
     }
-    if (t + 1 < ntiles) kv_store<C::LREG>(kvst, ks_lds[buf ^ 1], vs_lds[buf ^ 1], ldsk, ldsv);
+    if (t + 1 < ntiles + (TAIL ? 1 : 0)) kv_store<C::LREG>(kvst, ks_lds[buf ^ 1], vs_lds[buf ^ 1], ldsk, ldsv);
     __syncthreads();
   }
+  if constexpr (TAIL) {
+    // ---- segment B (peeled: the running max and sum, the rescale factors and the staging
+    // registers are dead here; as a run-time branch inside the loop it cost 20-60 VGPRs and
+    // spilled the QBLK 4 instances).  It holds `tail` keys; the rest of its tile are clamped
+    // duplicates and masked.
+    const int buf = ntiles & 1;
+    f32x4 s[4][QBLK];
+    qk_tile(ks_lds[buf], s);
+#pragma unroll
+    for (int kb = 0; kb < 4; ++kb)
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (4 * fg + kb * 16 + j >= tail) {
+#pragma unroll
+          for (int qb = 0; qb < QBLK; ++qb) s[kb][qb][j] = -INFINITY;
+        }
+    // segment A is complete: O /= l, the epilogue's arithmetic
+#pragma unroll
+    for (int qb = 0; qb < QBLK; ++qb) {
+      float l;
+      if constexpr (ONES) {
+        constexpr int a1 = D / 16, r1 = D % 16;
+        l = __shfl(oacc[a1][qb][r1 % 4], (r1 / 4) * 16 + fr, 64);
+      } else {
+        l = lrow[qb];
+        l += __shfl_xor(l, 16, 64);
+        l += __shfl_xor(l, 32, 64);
+      }
+      const float inv = 1.0f / l;
+#pragma unroll
+      for (int a = 0; a < C::DV / 16; ++a)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) oacc[a][qb][j] *= inv;
+    }
+    // one-pass softmax of segment B: P = exp2(s*c - m) / l
+    bf16x8 pf[2][QBLK];
+#pragma unroll
+    for (int qb = 0; qb < QBLK; ++qb) {
+      float mx = s[0][qb][0];
+#pragma unroll
+      for (int kb = 0; kb < 4; ++kb)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) mx = fmaxf(mx, s[kb][qb][j]);
+      mx = max_over_query_lanes(mx) * c;  // finite: key 0 of the segment is never masked
+      float ls = 0.f;
+#pragma unroll
+      for (int kb = 0; kb < 4; ++kb)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const float p = __builtin_amdgcn_exp2f(fmaf(s[kb][qb][j], c, -mx));
+          s[kb][qb][j] = p;
+          ls += p;
+        }
+      ls += __shfl_xor(ls, 16, 64);
+      ls += __shfl_xor(ls, 32, 64);
+      const float inv = 1.0f / ls;  // ls >= 1: the row max contributes exp2(0)
+#pragma unroll
+      for (int st = 0; st < 2; ++st) {
+        bf16x8 f;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          f[j] = (__bf16)(s[2 * st][qb][j] * inv);
+          f[4 + j] = (__bf16)(s[2 * st + 1][qb][j] * inv);
+        }
+        pf[st][qb] = f;
+      }
+    }
+    pv_tile(vs_lds[buf], pf);
+  }
 
-  // ---- epilogue: O[q][d] = O^T[d][q] / l
+  // ---- epilogue: O[q][d] = O^T[d][q] / l (a tailed call normalised each segment already)
 #pragma unroll
   for (int qb = 0; qb < QBLK; ++qb) {
-    float l;
-    if constexpr (ONES) {
-      constexpr int a1 = D / 16, r1 = D % 16;
-      l = __shfl(oacc[a1][qb][r1 % 4], (r1 / 4) * 16 + fr, 64);
-    } else {
-      l = lrow[qb];
-      l += __shfl_xor(l, 16, 64);
-      l += __shfl_xor(l, 32, 64);
+    float inv = 1.0f;
+    if constexpr (!TAIL) {
+      float l;
+      if constexpr (ONES) {
+        constexpr int a1 = D / 16, r1 = D % 16;
+        l = __shfl(oacc[a1][qb][r1 % 4], (r1 / 4) * 16 + fr, 64);
+      } else {
+        l = lrow[qb];
+        l += __shfl_xor(l, 16, 64);
+        l += __shfl_xor(l, 32, 64);
+      }
+      inv = 1.0f / l;
     }
-    const float inv = 1.0f / l;
     const int64_t qi = q0 + qb * 16 + fr;
     if (qi >= sq) continue;
     bf16_t* orow = o + (b * sq + qi) * ldo + (int64_t)h * D;
@@ -1805,6 +1966,28 @@ int launch_flash_causal(const void* q, int64_t ldq, const void* k, int64_t ldk, 
   return vd_launch_status();
 }
 
+// VD_ATTN_TAIL(n): always the 16x16x32 flash kernel's tailed instances, QBLK as above.
+template <int D>
+int launch_flash_tail(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
+                      void* o, int64_t ldo, int64_t batch, int heads, int64_t sq, int64_t skv, int64_t kv_div,
+                      float scale, hipStream_t s, int out_f32, int tail) {
+  const float c = scale * 1.4426950408889634f;
+  if constexpr (D <= 40) {
+    if (sq >= 1024) {
+      const dim3 grid((unsigned)((sq + 255) / 256), (unsigned)heads, (unsigned)batch);
+      hipLaunchKernelGGL((flash_attn_kernel<D, 4, false, true>), grid, dim3(NT), 0, s, (const bf16_t*)q, ldq,
+                         (const bf16_t*)k, ldk, (const bf16_t*)v, ldv, (bf16_t*)o, ldo, heads, sq, skv,
+                         kv_div, c, out_f32, tail);
+      return vd_launch_status();
+    }
+  }
+  const dim3 grid((unsigned)((sq + 127) / 128), (unsigned)heads, (unsigned)batch);
+  hipLaunchKernelGGL((flash_attn_kernel<D, 2, false, true>), grid, dim3(NT), 0, s, (const bf16_t*)q, ldq,
+                     (const bf16_t*)k, ldk, (const bf16_t*)v, ldv, (bf16_t*)o, ldo, heads, sq, skv,
+                     kv_div, c, out_f32, tail);
+  return vd_launch_status();
+}
+
 // ---------------------------------------------------------------- temporal
 // One wave per (b, p, h) item; lane = (query f = lane / LPQ, part = lane % LPQ);
 // 16-byte dim chunks c of the head are owned by part c % LPQ.
@@ -2271,8 +2454,19 @@ static int attention_entry(const void* q, int64_t ldq, const void* k, int64_t ld
   VD_CHECK_ARG(batch > 0 && heads > 0 && sq > 0 && skv > 0 && kv_div > 0 && batch % kv_div == 0);
   VD_CHECK_ARG(batch <= 65535 && heads <= 65535);
   VD_CHECK_ARG(skv * ldk < 0x7fffffff && skv * ldv < 0x7fffffff);
-  VD_CHECK_ARG(kernel >= 0 && (kernel & ~(0xff | VD_ATTN_CAUSAL)) == 0 && (kernel & 0xff) <= 3);
+  VD_CHECK_ARG(kernel >= 0 && (kernel & ~(0xff | VD_ATTN_CAUSAL | VD_ATTN_TAIL_MASK)) == 0 && (kernel & 0xff) <= 3);
   hipStream_t s = (hipStream_t)stream;
+  if (const int tail = (kernel & VD_ATTN_TAIL_MASK) >> VD_ATTN_TAIL_SHIFT) {
+    VD_CHECK_ARG(tail <= KT && tail < skv && !(kernel & VD_ATTN_CAUSAL) && scale > 0.f);
+    switch (d) {
+      case 32: return launch_flash_tail<32>(q, ldq, k, ldk, v, ldv, o, ldo, batch, heads, sq, skv, kv_div, scale, s, out_f32, tail);
+      case 40: return launch_flash_tail<40>(q, ldq, k, ldk, v, ldv, o, ldo, batch, heads, sq, skv, kv_div, scale, s, out_f32, tail);
+      case 64: return launch_flash_tail<64>(q, ldq, k, ldk, v, ldv, o, ldo, batch, heads, sq, skv, kv_div, scale, s, out_f32, tail);
+      case 80: return launch_flash_tail<80>(q, ldq, k, ldk, v, ldv, o, ldo, batch, heads, sq, skv, kv_div, scale, s, out_f32, tail);
+      case 160: return launch_flash_tail<160>(q, ldq, k, ldk, v, ldv, o, ldo, batch, heads, sq, skv, kv_div, scale, s, out_f32, tail);
+      default: return VD_EUNSUPPORTED;
+    }
+  }
   if (kernel & VD_ATTN_CAUSAL) {
     VD_CHECK_ARG(sq == skv && kv_div == 1 && scale > 0.f);
     switch (d) {

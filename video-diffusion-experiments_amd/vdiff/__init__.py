@@ -7,6 +7,8 @@ experiments) over hand-written gfx950 HIP kernels in libvdiff_hip.so.
 from .config import FULL, TINY, get_config  # noqa: F401
 from .models import UNetMotionModel, UNetMotionOutput  # noqa: F401
 from .models.clip import CLIPTextModel, CLIPTextModelOutput  # noqa: F401
+from .models.clip import CLIPVisionModelWithProjection, ImageProjection  # noqa: F401
+from .image_processor import CLIPImageProcessor  # noqa: F401
 from .models.dit import DiT3DModel, DiTDenoiseLoop, DiTOutput  # noqa: F401
 from .models.vae import (AutoencoderKL, AutoencoderKLOutput, DecoderOutput,  # noqa: F401
                          DiagonalGaussianDistribution)

@@ -36,12 +36,13 @@ Transformer2DModelOutput = namedtuple("Transformer2DModelOutput", ["sample"])
 class Ctx:
     """Per-forward state shared by every block (fast path)."""
 
-    def __init__(self, batch, frames, temb_all, ehs_rows, ctx_len, dist=None, kv_cache=None):
+    def __init__(self, batch, frames, temb_all, ehs_rows, ctx_len, dist=None, kv_cache=None, ip_rows=None):
         self.batch = batch            # videos in this forward (2 with CFG)
         self.frames = frames          # frames held by THIS rank
         self.temb_all = temb_all      # fp32 [batch, sum(resnet Cout)] = time_emb_proj(silu(temb))
         self.ehs_rows = ehs_rows      # bf16 [batch*ctx_len, D]
         self.ctx_len = ctx_len
+        self.ip_rows = ip_rows        # bf16 [batch*n, D]: IP-Adapter image tokens, or None
         self.dist = dist              # vdiff.dist.FrameShard or None
         self.kv_cache = kv_cache      # {id(attn): kv rows} or None
         # the two CFG halves of the input are the same latents (DenoiseLoop): everything before
@@ -226,8 +227,17 @@ class BasicTransformerBlock(nn.Module):
             h, n = self._out_norm(a, self.attn1, 2, h)
             q = self.fold(2, h.shape[0]).gemm(h) if n is None else ops.gemm(n, self.attn2._wq)
         kv = None if ctx.kv_cache is None else ctx.kv_cache.get(id(self.attn2))
+        # image-prompt tokens (IP-Adapter): each video's K/V rows are its text rows followed by
+        # its n image rows, attended as a second segment by the same launch (ops.attention tail)
+        skv, tail = ctx.ctx_len, {}
+        if ctx.ip_rows is not None:
+            n_ip = ctx.ip_rows.shape[0] // ctx.batch
+            skv, tail = ctx.ctx_len + n_ip, {"tail": n_ip}
         if kv is None:
-            kv = self.attn2.project_kv(ctx.ehs_rows)
+            if ctx.ip_rows is None:
+                kv = self.attn2.project_kv(ctx.ehs_rows)
+            else:
+                kv = self.attn2.project_kv(ctx.ehs_rows, ctx.ip_rows, ctx.batch)
             if ctx.kv_cache is not None:
                 ctx.kv_cache[id(self.attn2)] = kv
         if dup:  # the cross-attention of each guidance half on the shared q: no copy of q or h
@@ -235,11 +245,12 @@ class BasicTransformerBlock(nn.Module):
             a = torch.empty(2 * Mh, C, device=h.device, dtype=h.dtype)
             for g in range(2):
                 ops.attention(q, kv[g * L:(g + 1) * L, :C], kv[g * L:(g + 1) * L, C:], n_img, self.heads, hw,
-                              ctx.ctx_len, d, kv_div=ctx.frames, scale=self.attn2.attn_scale, out=a[g * Mh:(g + 1) * Mh])
+                              skv, d, kv_div=ctx.frames, scale=self.attn2.attn_scale, out=a[g * Mh:(g + 1) * Mh],
+                              **tail)
             h, n = self._out_norm_dup(a, self.attn2, 3, h)
         else:
-            a = ops.attention(q, kv[:, :C], kv[:, C:], n_img, self.heads, hw, ctx.ctx_len, d,
-                              kv_div=ctx.frames, scale=self.attn2.attn_scale)
+            a = ops.attention(q, kv[:, :C], kv[:, C:], n_img, self.heads, hw, skv, d,
+                              kv_div=ctx.frames, scale=self.attn2.attn_scale, **tail)
             h, n = self._out_norm(a, self.attn2, 3, h)
         return self._ff(h, n)
 

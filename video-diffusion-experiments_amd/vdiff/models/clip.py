@@ -86,13 +86,16 @@ class CLIPTextEmbeddings(nn.Module):
 
 
 class CLIPAttention(nn.Module):
-    def __init__(self, cfg):
+    def __init__(self, cfg, causal: bool = True):
         super().__init__()
         H = cfg["hidden_size"]
         self.num_heads = cfg["num_attention_heads"]
         self.head_dim = H // self.num_heads
-        if self.head_dim * self.num_heads != H or self.head_dim not in (32, 64):
-            raise NotImplementedError(f"CLIP head_dim {H} / {self.num_heads}: the causal flash kernel takes 32 or 64")
+        self.causal = causal  # the text tower; the vision tower attends to every patch
+        takes = (32, 64) if causal else (32, 40, 64, 80, 128, 160)
+        if self.head_dim * self.num_heads != H or self.head_dim not in takes:
+            raise NotImplementedError(f"CLIP head_dim {H} / {self.num_heads}: the {'causal ' if causal else ''}flash "
+                                      f"kernel takes one of {takes}")
         self.k_proj = Linear(H, H)
         self.v_proj = Linear(H, H)
         self.q_proj = Linear(H, H)
@@ -104,10 +107,13 @@ class CLIPAttention(nn.Module):
         self._wo, self._bo = bf(self.out_proj.weight), f32(self.out_proj.bias)
 
     def attend(self, n, B, S):
-        """Causal self-attention of the normed rows n: the fused q|k|v GEMM, then the flash kernel
-        on column slices of its output (q unscaled in bf16; the kernel applies head_dim^-1/2)."""
+        """Self-attention (causal in the text tower) of the normed rows n: the fused q|k|v GEMM,
+        then the flash kernel on column slices of its output (q unscaled in bf16; the kernel
+        applies head_dim^-1/2)."""
         H = self.num_heads * self.head_dim
         qkv = ops.gemm(n, self._wqkv, bias=self._bqkv)
+        if not self.causal:
+            return ops.attention(qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], B, self.num_heads, S, S, self.head_dim)
         return ops.attention(qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], B, self.num_heads, S, S, self.head_dim,
                              causal=True)
 
@@ -127,10 +133,10 @@ class CLIPMLP(nn.Module):
 
 
 class CLIPEncoderLayer(nn.Module):
-    def __init__(self, cfg):
+    def __init__(self, cfg, causal: bool = True):
         super().__init__()
         eps = cfg["layer_norm_eps"]
-        self.self_attn = CLIPAttention(cfg)
+        self.self_attn = CLIPAttention(cfg, causal=causal)
         self.layer_norm1 = LayerNorm(cfg["hidden_size"], eps=eps)
         self.mlp = CLIPMLP(cfg)
         self.layer_norm2 = LayerNorm(cfg["hidden_size"], eps=eps)
@@ -146,9 +152,9 @@ class CLIPEncoderLayer(nn.Module):
 
 
 class CLIPEncoder(nn.Module):
-    def __init__(self, cfg):
+    def __init__(self, cfg, causal: bool = True):
         super().__init__()
-        self.layers = nn.ModuleList([CLIPEncoderLayer(cfg) for _ in range(cfg["num_hidden_layers"])])
+        self.layers = nn.ModuleList([CLIPEncoderLayer(cfg, causal=causal) for _ in range(cfg["num_hidden_layers"])])
 
 
 class CLIPTextTransformer(nn.Module):
@@ -227,3 +233,196 @@ class CLIPTextModel(nn.Module):
         hs = tuple(t.view(B, S, -1) for t in hidden) if output_hidden_states else None
         out = CLIPTextModelOutput(last, pooled, hs)
         return out if return_dict else out.to_tuple()
+
+
+# ---------------------------------------------------------------------------- vision tower
+# transformers.CLIPVisionModelWithProjection, the IP-Adapter's image encoder (ViT-H/14 in the
+# SD-1.5 adapters: hidden 1280, 16 heads of d = 80, 257 tokens; ViT-L/14 has d = 64).  Parameter
+# names are transformers' own, `pre_layrnorm` included:
+#
+#     vision_model.embeddings.{class_embedding, patch_embedding.weight, position_embedding.weight}
+#     vision_model.pre_layrnorm, vision_model.encoder.layers.N.*, vision_model.post_layernorm
+#     visual_projection.weight
+#
+# Device path: the patch embedding (a stride-p p x p convolution without bias) is the patch rows
+# [(b, gy, gx)][3 p^2] times one GEMM with fp32 output, K zero-padded to a multiple of 8; class
+# token and position rows are added in fp32 and the sum is rounded once; then the text tower's
+# encoder layers with the non-causal flash attention.  Runs once per video.
+CLIP_VIT_H14 = dict(hidden_size=1280, intermediate_size=5120, num_hidden_layers=32, num_attention_heads=16,
+                    image_size=224, patch_size=14, num_channels=3, hidden_act="gelu", layer_norm_eps=1e-5,
+                    projection_dim=1024)
+CLIP_VISION_TINY = dict(hidden_size=64, intermediate_size=128, num_hidden_layers=2, num_attention_heads=2,
+                        image_size=56, patch_size=14, num_channels=3, hidden_act="quick_gelu", layer_norm_eps=1e-5,
+                        projection_dim=48)
+CLIP_VISION_CONFIGS = {"vit_h14": CLIP_VIT_H14, "tiny": CLIP_VISION_TINY}
+
+
+def clip_vision_config(config) -> dict:
+    """A named config ("vit_h14", "tiny") or a transformers CLIPVisionConfig dict (unknown keys kept)."""
+    if isinstance(config, str):
+        if config not in CLIP_VISION_CONFIGS:
+            raise KeyError(f"unknown CLIP vision config {config!r}: one of {sorted(CLIP_VISION_CONFIGS)} or a dict")
+        return dict(CLIP_VISION_CONFIGS[config])
+    cfg = dict(CLIP_VIT_H14)
+    cfg.update({k: v for k, v in dict(config).items() if v is not None})
+    return cfg
+
+
+class CLIPVisionModelOutput:
+    """transformers' CLIPVisionModelOutput: image_embeds, last_hidden_state, hidden_states."""
+
+    def __init__(self, image_embeds, last_hidden_state, hidden_states=None):
+        self.image_embeds = image_embeds
+        self.last_hidden_state = last_hidden_state
+        self.hidden_states = hidden_states
+
+    def to_tuple(self):
+        t = (self.image_embeds, self.last_hidden_state)
+        return t if self.hidden_states is None else t + (self.hidden_states,)
+
+    def __getitem__(self, i):
+        return self.to_tuple()[i]
+
+
+class CLIPVisionEmbeddings(nn.Module):
+    def __init__(self, cfg):
+        super().__init__()
+        H, p = cfg["hidden_size"], cfg["patch_size"]
+        self.patch_size, self.image_size, self.num_channels = p, cfg["image_size"], cfg["num_channels"]
+        self.class_embedding = nn.Parameter(torch.zeros(H))
+        self.patch_embedding = nn.Conv2d(self.num_channels, H, kernel_size=p, stride=p, bias=False)
+        self.num_positions = (self.image_size // p) ** 2 + 1
+        self.position_embedding = nn.Embedding(self.num_positions, H)
+
+    def prepare(self):
+        w = self.patch_embedding.weight
+        k = w[0].numel()
+        self._kpad = (k + 7) // 8 * 8
+        wp = torch.zeros(w.shape[0], self._kpad, device=w.device, dtype=torch.float32)
+        wp[:, :k] = w.reshape(w.shape[0], k).float()
+        self._wp = bf(wp)
+
+    def rows(self, pixel_values):
+        """bf16 rows [(b, token)][H]: [class ; patch GEMM] + position rows, summed in fp32, rounded once."""
+        B, Cc, Hh, Ww = pixel_values.shape
+        p = self.patch_size
+        if Cc != self.num_channels or Hh != self.image_size or Ww != self.image_size:
+            raise ValueError(f"pixel_values of shape {tuple(pixel_values.shape)}: expected "
+                             f"(B, {self.num_channels}, {self.image_size}, {self.image_size})")
+        g = Hh // p
+        x = pixel_values.to(torch.bfloat16).reshape(B, Cc, g, p, g, p).permute(0, 2, 4, 1, 3, 5).reshape(B * g * g, -1)
+        a = torch.zeros(B * g * g, self._kpad, device=x.device, dtype=torch.bfloat16)
+        a[:, :x.shape[1]] = x
+        patches = ops.gemm(a, self._wp, out_f32=True).view(B, g * g, -1)
+        cls = self.class_embedding.float().expand(B, 1, -1)
+        h = torch.cat([cls, patches], 1) + self.position_embedding.weight.float()
+        return h.to(torch.bfloat16).reshape(B * (g * g + 1), -1)
+
+
+class CLIPVisionTransformer(nn.Module):
+    def __init__(self, cfg):
+        super().__init__()
+        eps = cfg["layer_norm_eps"]
+        self.embeddings = CLIPVisionEmbeddings(cfg)
+        self.pre_layrnorm = LayerNorm(cfg["hidden_size"], eps=eps)  # transformers' spelling
+        self.encoder = CLIPEncoder(cfg, causal=False)
+        self.post_layernorm = LayerNorm(cfg["hidden_size"], eps=eps)
+
+
+class CLIPVisionModelWithProjection(nn.Module):
+    """transformers.CLIPVisionModelWithProjection("vit_h14" | "tiny" | config dict): pixel values
+    (B, 3, S, S) -> image_embeds (B, projection_dim), last_hidden_state and, on request, the
+    hidden states (the encoder's input after pre_layrnorm first, as transformers lists them)."""
+
+    def __init__(self, config="vit_h14"):
+        super().__init__()
+        self.config = clip_vision_config(config)
+        self.vision_model = CLIPVisionTransformer(self.config)
+        self.visual_projection = Linear(self.config["hidden_size"], self.config["projection_dim"], bias=False)
+        self._prepared = False
+
+    @property
+    def device(self):
+        return self.visual_projection.weight.device
+
+    @property
+    def dtype(self):
+        return self.visual_projection.weight.dtype
+
+    def prepare(self):
+        for m in self.modules():
+            if isinstance(m, (CLIPAttention, CLIPMLP, LayerNorm, CLIPVisionEmbeddings)):
+                m.prepare()
+        self._wproj = bf(self.visual_projection.weight)
+        self._prepared = True
+        return self
+
+    def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
+        sd = {k: v for k, v in state_dict.items() if not k.endswith("embeddings.position_ids")}
+        out = super().load_state_dict(sd, strict=strict, assign=assign)
+        self._prepared = False
+        return out
+
+    def forward(self, pixel_values, output_hidden_states=False, return_dict=True, **unused):
+        if not pixel_values.is_cuda:
+            raise ValueError("vdiff modules run on the GPU only (got a CPU tensor); no CPU fallback")
+        if not self._prepared:
+            self.prepare()
+        vm = self.vision_model
+        B = pixel_values.shape[0]
+        e = vm.embeddings.rows(pixel_values)
+        S = e.shape[0] // B
+        pre = vm.pre_layrnorm
+        h = ops.layer_norm(e, pre._g, pre._b, eps=pre.eps)
+        layers = list(vm.encoder.layers)
+        hidden = [h]
+        first = layers[0].layer_norm1 if layers else vm.post_layernorm
+        n = ops.layer_norm(h, first._g, first._b, eps=first.eps)
+        for i, layer in enumerate(layers):
+            nxt = layers[i + 1].layer_norm1 if i + 1 < len(layers) else vm.post_layernorm
+            h, n = layer.run(h, n, B, S, nxt)
+            hidden.append(h)
+        pooled = n.view(B, S, -1)[:, 0].contiguous()  # post_layernorm of the class token
+        embeds = ops.gemm(pooled, self._wproj)
+        hs = tuple(t.view(B, S, -1) for t in hidden) if output_hidden_states else None
+        out = CLIPVisionModelOutput(embeds, h.view(B, S, -1), hs)
+        return out if return_dict else out.to_tuple()
+
+
+class ImageProjection(nn.Module):
+    """diffusers' ImageProjection (the plain IP-Adapter's image_proj): Linear(clip_dim ->
+    n * cross_dim), reshape to (B, n, cross_dim), LayerNorm.  State-dict keys as the adapter
+    checkpoint's `image_proj.` group: proj.{weight,bias}, norm.{weight,bias}."""
+
+    def __init__(self, image_embed_dim: int, cross_attention_dim: int, num_image_text_embeds: int):
+        super().__init__()
+        self.num_image_text_embeds, self.cross_attention_dim = num_image_text_embeds, cross_attention_dim
+        self.proj = Linear(image_embed_dim, num_image_text_embeds * cross_attention_dim)
+        self.norm = LayerNorm(cross_attention_dim)
+
+    @classmethod
+    def from_state_dict(cls, sd: dict, cross_attention_dim: int):
+        """The token count comes from the checkpoint: proj.weight.shape[0] // cross_attention_dim."""
+        w = sd["proj.weight"]
+        if w.shape[0] % cross_attention_dim:
+            raise ValueError(f"image_proj.proj.weight has {w.shape[0]} rows: no multiple of cross_attention_dim "
+                             f"{cross_attention_dim}")
+        m = cls(w.shape[1], cross_attention_dim, w.shape[0] // cross_attention_dim)
+        m.load_state_dict(sd, strict=True)
+        return m
+
+    def prepare(self):
+        self._w, self._b = bf(self.proj.weight), f32(self.proj.bias)
+        self.norm.prepare()
+        return self
+
+    def forward(self, image_embeds):
+        """(B, clip_dim) or (B, 1, clip_dim) -> bf16 (B, n, cross_dim) on the HIP GEMM + LayerNorm."""
+        if not image_embeds.is_cuda:
+            raise ValueError("vdiff modules run on the GPU only (got a CPU tensor); no CPU fallback")
+        if getattr(self, "_w", None) is None:
+            self.prepare()
+        x = image_embeds.reshape(image_embeds.shape[0], -1).to(torch.bfloat16).contiguous()
+        y = ops.gemm(x, self._w, bias=self._b).view(x.shape[0] * self.num_image_text_embeds, self.cross_attention_dim)
+        y = ops.layer_norm(y, self.norm._g, self.norm._b, eps=self.norm.eps)
+        return y.view(x.shape[0], self.num_image_text_embeds, self.cross_attention_dim)

@@ -426,9 +426,58 @@ class Attention(nn.Module):
         else:
             self._wqkv = bf(torch.cat([wq, self.to_k.weight.float(), self.to_v.weight.float()], 0))
         self._wo, self._bo = bf(self.to_out[0].weight), f32(self.to_out[0].bias)
+        self.prepare_ip()
 
-    def project_kv(self, ctx_rows):
-        return ops.gemm(ctx_rows, self._wkv)
+    # IP-Adapter (image prompt): to_k_ip / to_v_ip exist only on a spatial cross-attention and
+    # only while an adapter is loaded; without them parameters, state_dict and operands are
+    # those of the plain module.  The adapter scale is folded into the packed V rows (fp32
+    # multiply, one bf16 rounding), so the two-segment attention kernel needs no scale argument.
+    ip_scale = 1.0
+
+    def add_ip_adapter(self, w_k: torch.Tensor, w_v: torch.Tensor):
+        if not self.is_cross:
+            raise ValueError("an IP-Adapter attaches to cross-attentions only")
+        inner = self.heads * self.dim_head
+        if tuple(w_k.shape) != tuple(w_v.shape) or w_k.shape[0] != inner:
+            raise ValueError(f"to_k_ip / to_v_ip of shapes {tuple(w_k.shape)} / {tuple(w_v.shape)} "
+                             f"do not fit {inner} attention channels")
+        ref = self.to_k.weight
+        for name, w in (("to_k_ip", w_k), ("to_v_ip", w_v)):
+            lin = Linear(w.shape[1], inner, bias=False)
+            lin.weight = nn.Parameter(w.detach().to(ref.device, ref.dtype).clone(), requires_grad=False)
+            setattr(self, name, lin)
+
+    def remove_ip_adapter(self):
+        for name in ("to_k_ip", "to_v_ip"):
+            if name in self._modules:
+                delattr(self, name)
+        self.__dict__.pop("_wkv_ip", None)
+        self.__dict__.pop("ip_scale", None)
+
+    def prepare_ip(self, scale: Optional[float] = None):
+        """Pack [to_k_ip ; s * to_v_ip] (nothing to do without an adapter)."""
+        if "to_k_ip" not in self._modules:
+            return
+        if scale is not None:
+            self.ip_scale = float(scale)
+        self._wkv_ip = bf(torch.cat([self.to_k_ip.weight.float(), self.ip_scale * self.to_v_ip.weight.float()], 0))
+
+    def project_kv(self, ctx_rows, ip_rows=None, batch=1):
+        """K | V rows of the text.  With ip_rows (bf16 [batch * n, cross_dim], the projected image
+        tokens) the result is one [batch * (L + n), 2C] buffer: per video L text rows, then the
+        n image rows [k_ip | s * v_ip] — the row layout of ops.attention(tail=n).  Each GEMM
+        writes its row slice of the buffer; nothing is copied."""
+        if ip_rows is None:
+            return ops.gemm(ctx_rows, self._wkv)
+        if getattr(self, "_wkv_ip", None) is None:
+            raise RuntimeError("image-prompt tokens given, but this attention has no IP-Adapter loaded")
+        L, n = ctx_rows.shape[0] // batch, ip_rows.shape[0] // batch
+        kv = torch.empty(batch * (L + n), self._wkv.shape[0], device=ctx_rows.device, dtype=ctx_rows.dtype)
+        for b in range(batch):
+            r = b * (L + n)
+            ops.gemm(ctx_rows[b * L:(b + 1) * L], self._wkv, out=kv[r:r + L])
+            ops.gemm(ip_rows[b * n:(b + 1) * n], self._wkv_ip, out=kv[r + L:r + L + n])
+        return kv
 
     def forward(self, hidden_states, encoder_hidden_states=None, attention_mask=None, **cross_attention_kwargs):
         """AttnProcessor2_0 over (N, S, C) tokens: to_q/to_k/to_v modules, softmax(q k^T /
@@ -436,6 +485,9 @@ class Attention(nn.Module):
         sequence is a motion module's <= 32 frames), to_out modules."""
         if attention_mask is not None:
             raise NotImplementedError("attention_mask is not used by the reference's pipeline")
+        if isinstance(encoder_hidden_states, (tuple, list)):
+            raise NotImplementedError("(encoder_hidden_states, ip_hidden_states): the module path is text-only; "
+                                      "image prompts run on the fast path (DenoiseLoop(ip_embeds=...))")
         x = to_bf16_cuda(hidden_states)
         ctx = x if encoder_hidden_states is None else to_bf16_cuda(encoder_hidden_states)
         N, S, _ = x.shape

@@ -115,10 +115,53 @@ class UNetMotionModel(nn.Module):
         return self
 
     # ------------------------------------------------------------------ core
-    def make_ctx(self, t_emb_bf16, ehs_rows, batch, frames, ctx_len, kv_cache=None):
+    def make_ctx(self, t_emb_bf16, ehs_rows, batch, frames, ctx_len, kv_cache=None, ip_rows=None):
         temb_silu = self.time_embedding.forward_silu(t_emb_bf16)
         temb_all = ops.gemm(temb_silu, self._w_temb, bias=self._b_temb, out_f32=True)
-        return Ctx(batch, frames, temb_all, ehs_rows, ctx_len, dist=self.dist, kv_cache=kv_cache)
+        return Ctx(batch, frames, temb_all, ehs_rows, ctx_len, dist=self.dist, kv_cache=kv_cache, ip_rows=ip_rows)
+
+    # ------------------------------------------------------------------ IP-Adapter
+    def spatial_cross_attentions(self):
+        """The non-motion cross-attentions (attn2 of every spatial transformer block) in the
+        order an IP-Adapter checkpoint numbers them: down_blocks, up_blocks, mid_block
+        (vdiff.pretrained.IP_ADAPTER_BLOCK_ORDER)."""
+        from ..pretrained import IP_ADAPTER_BLOCK_ORDER
+        out = []
+        for name in IP_ADAPTER_BLOCK_ORDER:
+            blks = getattr(self, name)
+            for blk in (blks if isinstance(blks, nn.ModuleList) else [blks]):
+                for tm in getattr(blk, "attentions", None) or []:
+                    out.extend(tb.attn2 for tb in tm.transformer_blocks)
+        return out
+
+    @property
+    def has_ip_adapter(self) -> bool:
+        return any("to_k_ip" in a._modules for a in self.spatial_cross_attentions())
+
+    @torch.no_grad()
+    def set_ip_adapter_weights(self, kv_weights, scale: float = 1.0):
+        """kv_weights: one (to_k_ip.weight, to_v_ip.weight) pair per spatial cross-attention, in
+        spatial_cross_attentions() order."""
+        attns = self.spatial_cross_attentions()
+        if len(kv_weights) != len(attns):
+            raise ValueError(f"{len(kv_weights)} to_k_ip / to_v_ip pairs for {len(attns)} cross-attentions")
+        for a, (wk, wv) in zip(attns, kv_weights):
+            a.add_ip_adapter(wk, wv)
+        self.set_ip_adapter_scale(scale)
+
+    @torch.no_grad()
+    def set_ip_adapter_scale(self, scale: float):
+        """Re-packs only the [to_k_ip ; s * to_v_ip] operands (the scale lives in the V rows)."""
+        if not isinstance(scale, (int, float)):
+            raise NotImplementedError("per-block IP-Adapter scales (a dict or list) are not supported: one float")
+        for a in self.spatial_cross_attentions():
+            a.ip_scale = float(scale)
+            if self._prepared:
+                a.prepare_ip()
+
+    def unload_ip_adapter(self):
+        for a in self.spatial_cross_attentions():
+            a.remove_ip_adapter()
 
     def forward_rows(self, x_rows, h, w, ctx: Ctx):
         """Packed NHWC input rows [batch*frames*h*w, 8] -> eps rows fp32 [..., out_channels]."""

@@ -522,15 +522,23 @@ def layer_norm(x, gamma, beta, eps=1e-5, pe=None, pe_div=1, pe_period=1, out=Non
 # ---------------------------------------------------------------- attention
 ATTN_KERNELS = {"auto": 0, "v1": 1, "flash32": 2, "flash40": 3}
 ATTN_CAUSAL = 0x100  # VD_ATTN_CAUSAL, OR-ed into vd_attention_ex's kernel argument
+ATTN_TAIL_SHIFT = 16  # VD_ATTN_TAIL(n) = n << 16, n in 1..64 (mask 0x7f0000)
 ATTN_TAP = None  # bench hook: callable(q, k, v, batch, heads, sq, skv, d, scale) seen by every attention call
 
 
 def attention(q, k, v, batch, heads, sq, skv, d, kv_div=1, scale=None, out=None, out_f32=False, kernel="auto",
-              causal=False):
+              causal=False, tail=0):
     """q/k/v: 2-D row views (may be column slices of a fused QKV buffer).  out_f32: O in fp32
     (the tests' north-star-tolerance mode).  kernel: "auto" (the product choice) or, for the
     parity tests, "v1" / "flash32" / "flash40" (vd_attention_ex).  causal: query i attends to
-    keys j <= i (VD_ATTN_CAUSAL: sq == skv, kv_div == 1, d 32 or 64; the CLIP text encoder)."""
+    keys j <= i (VD_ATTN_CAUSAL: sq == skv, kv_div == 1, d 32 or 64; the CLIP text encoder).
+    tail: n in 1..64 makes the call two-segment (VD_ATTN_TAIL(n), the IP-Adapter image prompt).
+    Row layout: each key batch still owns skv consecutive rows of k and v; rows [0, skv - n) are
+    segment A (the text), rows [skv - n, skv) segment B (the image tokens), and the result is
+    softmax(q K_A^T) V_A + softmax(q K_B^T) V_B — any adapter scale is already folded into V_B.
+    d in {32, 40, 64, 80, 160}, n < skv, never with causal."""
+    if not 0 <= tail <= 0x7f:
+        raise ValueError(f"tail must be in 0..127 to fit VD_ATTN_TAIL_MASK, got {tail}")
     _dev(q, k, v, out)
     if out is None:
         out = torch.empty(batch * sq, heads * d, device=q.device, dtype=torch.float32 if out_f32 else BF16)
@@ -539,7 +547,8 @@ def attention(q, k, v, batch, heads, sq, skv, d, kv_div=1, scale=None, out=None,
         ATTN_TAP(q, k, v, batch, heads, sq, skv, d, scale)
     check(lib().vd_attention_ex(_p(q), q.stride(0), _p(k), k.stride(0), _p(v), v.stride(0), _p(out), out.stride(0),
                                 batch, heads, sq, skv, d, kv_div, scale, int(out_f32),
-                                ATTN_KERNELS[kernel] | (ATTN_CAUSAL if causal else 0), _stream()), "vd_attention_ex")
+                                ATTN_KERNELS[kernel] | (ATTN_CAUSAL if causal else 0) | (tail << ATTN_TAIL_SHIFT),
+                                _stream()), "vd_attention_ex")
     return out
 
 

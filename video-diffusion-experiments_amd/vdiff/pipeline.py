@@ -44,6 +44,7 @@ from __future__ import annotations
 
 import zlib
 from collections import namedtuple
+from pathlib import Path
 
 import torch
 
@@ -74,8 +75,12 @@ class DenoiseLoop:
 
     def __init__(self, unet: UNetMotionModel, scheduler, latents: torch.Tensor,
                  prompt_embeds: torch.Tensor, guidance_scale: float, timesteps=None,
-                 use_graph: bool = True, cfg_shard=None):
-        """cfg_shard (vdiff.dist.CfgShard, CFG only): this rank runs the UNet on ONE half
+                 use_graph: bool = True, cfg_shard=None, ip_embeds=None):
+        """ip_embeds: the projected IP-Adapter image tokens [Bt, n, cross_attention_dim] (uncond
+        half first under CFG), or None.  They become n extra K/V rows per video in every spatial
+        cross-attention (built once, in prime()'s eager step) and the attention launches take
+        them as a second softmax segment; not supported together with cfg_shard.
+        cfg_shard (vdiff.dist.CfgShard, CFG only): this rank runs the UNet on ONE half
         (cfg_shard.index: 0 uncond, 1 cond) and swaps eps rows with its pair before the
         fused CFG+scheduler update, which both ranks apply to their replicated latents
         (SURVEY.md §8e (ii)).  prompt_embeds still holds both halves, uncond first."""
@@ -112,6 +117,17 @@ class DenoiseLoop:
             pe = pe[h * self.B:(h + 1) * self.B].contiguous()
             self.Bu = self.B
         self.ehs_rows = pe.reshape(self.Bu * self.L, -1)
+        self.ip_rows = None
+        if ip_embeds is not None:
+            if self.cfg_shard is not None:
+                raise NotImplementedError("ip_embeds together with cfg_shard is not supported")
+            if not unet.has_ip_adapter:
+                raise ValueError("ip_embeds given, but the UNet has no IP-Adapter loaded")
+            ip = ip_embeds.to(dev, torch.bfloat16).contiguous()
+            if ip.dim() != 3 or ip.shape[0] != self.Bt or ip.shape[2] != pe.shape[-1] or not 1 <= ip.shape[1] <= 64:
+                raise ValueError(f"ip_embeds of shape {tuple(ip.shape)}: expected [{self.Bt}, n <= 64, {pe.shape[-1]}] "
+                                 "(uncond first when CFG)")
+            self.ip_rows = ip.reshape(self.Bt * ip.shape[1], -1)
         # the CFG step kernel writes the next input for both halves; under cfg_shard the
         # UNet reads only the first copy (the latents are replicated over the pair)
         self.x_in2 = ops.pack_latents(self.lat, dup=self.ncfg, cpad=CIN_PAD, in_div=self.in_div0)
@@ -136,7 +152,7 @@ class DenoiseLoop:
     def step(self):
         u = self.unet
         te = ops.timestep_embed(self.ts, u.time_proj.num_channels, step_idx=self.step_idx, batch=self.Bu)
-        ctx = u.make_ctx(te, self.ehs_rows, self.Bu, self.F, self.L, kv_cache=self.kv_cache)
+        ctx = u.make_ctx(te, self.ehs_rows, self.Bu, self.F, self.L, kv_cache=self.kv_cache, ip_rows=self.ip_rows)
         ctx.cfg_dup = self.cfg_dedup and self.Bu == self.Bt == 2 * self.B  # x_in = [lat; lat]
         eps = u.forward_rows(self.x_in, self.H, self.W, ctx)
         if self.cfg_shard is not None:
@@ -239,6 +255,10 @@ class AnimateDiffPipeline:
         self.vae = vae
         self.dist = dist
         self.unet.dist = dist
+        # IP-Adapter (load_ip_adapter): the CLIP vision tower, its preprocessing, the projection
+        self.image_encoder = None
+        self.feature_extractor = None
+        self.image_projection = None
         # the dtype the initial noise is drawn in (diffusers: prompt_embeds.dtype, i.e. the
         # pipeline's torch_dtype, fp32 when none is given); from_config keeps the reference's fp16
         self.torch_dtype = None
@@ -301,6 +321,107 @@ class AnimateDiffPipeline:
     def to(self, *a, **k):
         return self
 
+    # ------------------------------------------------------------------ IP-Adapter
+    def load_ip_adapter(self, pretrained_model_name_or_path_or_dict, subfolder=None,
+                        weight_name=None, image_encoder_folder="image_encoder", **unused):
+        """diffusers' load_ip_adapter over LOCAL files (vdiff.pretrained.read_ip_adapter): the plain
+        adapter's image_proj.* become self.image_projection, its ip_adapter.{id}.to_k_ip / to_v_ip
+        weights go to the UNet's spatial cross-attentions (ids 1, 3, 5, ... in
+        pretrained.IP_ADAPTER_BLOCK_ORDER).  image_encoder_folder (relative to subfolder when it
+        has no "/", as diffusers) is loaded as a vdiff.CLIPVisionModelWithProjection when the
+        pipeline has no image encoder yet and the folder exists; without one only
+        ip_adapter_image_embeds= can be used.  The scale starts at 1.0."""
+        from . import pretrained as P
+        from .image_processor import CLIPImageProcessor
+        from .models.clip import ImageProjection
+        src = pretrained_model_name_or_path_or_dict
+        image_proj, ip = P.read_ip_adapter(src, subfolder, weight_name or P.IP_ADAPTER_WEIGHT_NAME)
+        P.check_ip_adapter_variant(image_proj, ip)
+        unet = self.unet
+        cross = unet.config["cross_attention_dim"]
+        kv = P.ip_adapter_kv_weights(ip, len(unet.spatial_cross_attentions()))
+        proj = ImageProjection.from_state_dict(image_proj, cross)
+        if not 1 <= proj.num_image_text_embeds <= 64:
+            raise NotImplementedError(f"{proj.num_image_text_embeds} image tokens: the attention tail holds 1..64")
+        unet.unload_ip_adapter()  # a second load replaces the first; an image encoder already set is kept
+        unet.set_ip_adapter_weights(kv, scale=1.0)
+        self.image_projection = proj.to(device=unet.device, dtype=torch.bfloat16)
+        if unet.device.type == "cuda":
+            self.image_projection.prepare()
+        if self.image_encoder is None and image_encoder_folder is not None and not isinstance(src, dict):
+            root = P._local_dir(src, "load_ip_adapter")
+            rel = Path(image_encoder_folder)
+            folder = root / rel if "/" in str(image_encoder_folder) or not subfolder else root / subfolder / rel
+            if folder.is_dir():
+                self.image_encoder = P.load_image_encoder(folder, device=unet.device)
+        if self.feature_extractor is None:
+            size = 224 if self.image_encoder is None else self.image_encoder.config["image_size"]
+            self.feature_extractor = CLIPImageProcessor(size=size, crop_size=size)
+        return self
+
+    def unload_ip_adapter(self):
+        """Back to the text-only pipeline: the UNet's parameters, state_dict keys, prepared operands
+        and launches are those of a model that never loaded an adapter."""
+        self.unet.unload_ip_adapter()
+        self.image_projection = None
+        self.image_encoder = None
+        self.feature_extractor = None
+
+    def set_ip_adapter_scale(self, scale):
+        if self.image_projection is None:
+            raise ValueError("set_ip_adapter_scale: no IP-Adapter loaded")
+        self.unet.set_ip_adapter_scale(scale)
+
+    def encode_image(self, image):
+        """(image_embeds, zeros_like(image_embeds)) as diffusers' encode_image without hidden states:
+        bf16 (B, clip_dim) from the CLIP vision tower."""
+        if self.image_encoder is None:
+            raise ValueError("ip_adapter_image needs an image encoder: load_ip_adapter(..., image_encoder_folder=...) "
+                             "or pipe.image_encoder = vdiff.CLIPVisionModelWithProjection(...)")
+        if not isinstance(image, torch.Tensor) or image.dim() != 4:
+            image = self.feature_extractor(image, return_tensors="pt").pixel_values
+        e = self.image_encoder(image.to(self.image_encoder.device, torch.bfloat16)).image_embeds
+        return e, torch.zeros_like(e)
+
+    def prepare_ip_adapter_image_embeds(self, ip_adapter_image, ip_adapter_image_embeds, n_prompts,
+                                        num_videos_per_prompt, do_cfg):
+        """The projected image tokens [Bt, n, cross_attention_dim] for DenoiseLoop (uncond half
+        first under CFG), or None when neither argument is given.  diffusers' order: image_embeds
+        from the encoder, the negative zeros_like, [negative; positive] under CFG, each
+        repeat_interleave'd by num_videos_per_prompt, then the projection.  Precomputed embeds are
+        (B, 1, clip_dim), or (2B, 1, clip_dim) with the negative half first under CFG.  One image
+        for several prompts is shared by all of them."""
+        if ip_adapter_image is None and ip_adapter_image_embeds is None:
+            return None
+        if self.image_projection is None:
+            raise ValueError("ip_adapter_image / ip_adapter_image_embeds given, but no IP-Adapter is loaded "
+                             "(pipe.load_ip_adapter(...))")
+        if ip_adapter_image is not None and ip_adapter_image_embeds is not None:
+            raise ValueError("pass ip_adapter_image or ip_adapter_image_embeds, not both")
+        dev = self.unet.device
+        if ip_adapter_image_embeds is not None:
+            e = ip_adapter_image_embeds
+            if isinstance(e, (list, tuple)):
+                if len(e) != 1:
+                    raise NotImplementedError("a list of IP-Adapters (multiple image prompts) is not supported")
+                e = e[0]
+            e = e.to(dev, torch.bfloat16)
+            e = e.reshape(e.shape[0], -1)
+            neg, pos = e.chunk(2) if do_cfg else (None, e)
+        else:
+            pos, neg = self.encode_image(ip_adapter_image)
+            if not do_cfg:
+                neg = None
+        if pos.shape[0] == 1 and n_prompts > 1:
+            pos = pos.expand(n_prompts, -1)
+            neg = None if neg is None else neg.expand(n_prompts, -1)
+        if pos.shape[0] != n_prompts:
+            raise ValueError(f"{pos.shape[0]} image prompts for {n_prompts} prompts")
+        pos = pos.repeat_interleave(num_videos_per_prompt, 0)
+        if neg is not None:
+            pos = torch.cat([neg.repeat_interleave(num_videos_per_prompt, 0), pos])
+        return self.image_projection(pos.contiguous())
+
     def encode_prompt(self, prompt, batch, clip_skip=None):
         """(batch, 77, dim) embeddings of a prompt or a list of prompts.  With a tokenizer and a
         CLIPTextModel: the whole list is tokenized (padding="max_length", truncation) and encoded
@@ -361,7 +482,8 @@ class AnimateDiffPipeline:
     def __call__(self, prompt=None, num_frames=16, height=None, width=None, num_inference_steps=50,
                  guidance_scale=7.5, negative_prompt=None, num_videos_per_prompt=1, eta=0.0,
                  generator=None, latents=None, prompt_embeds=None, negative_prompt_embeds=None,
-                 output_type="pil", return_dict=True, use_graph=True, clip_skip=None, **unused):
+                 output_type="pil", return_dict=True, use_graph=True, clip_skip=None,
+                 ip_adapter_image=None, ip_adapter_image_embeds=None, **unused):
         if eta != 0.0:
             raise NotImplementedError("eta > 0")
         if output_type not in ("latent", "pt", "np", "pil"):
@@ -397,6 +519,8 @@ class AnimateDiffPipeline:
             ehs = torch.cat([negative_prompt_embeds.to(prompt_embeds), prompt_embeds])
         else:
             ehs = prompt_embeds
+        ip_embeds = self.prepare_ip_adapter_image_embeds(ip_adapter_image, ip_adapter_image_embeds,
+                                                         B // num_videos_per_prompt, num_videos_per_prompt, do_cfg)
         self.scheduler.set_timesteps(num_inference_steps)
         latents = self.prepare_latents(B, num_frames, h, w, generator=generator, latents=latents)
         local = latents
@@ -404,7 +528,7 @@ class AnimateDiffPipeline:
             fl = self.dist.frames_local(num_frames)
             local = latents[:, :, self.dist.rank * fl:(self.dist.rank + 1) * fl]
         loop = DenoiseLoop(self.unet, self.scheduler, local, ehs, guidance_scale,
-                           use_graph=use_graph).prime()
+                           use_graph=use_graph, ip_embeds=ip_embeds).prime()
         out = loop.run()
         if self.dist is not None:
             out = self.dist.all_gather_frames(out)
@@ -513,7 +637,8 @@ class AnimateDiffVideoToVideoPipeline(AnimateDiffPipeline):
     def __call__(self, video=None, prompt=None, negative_prompt=None, height=None, width=None,
                  num_inference_steps=50, guidance_scale=7.5, strength=0.8, num_videos_per_prompt=1, eta=0.0,
                  generator=None, latents=None, prompt_embeds=None, negative_prompt_embeds=None,
-                 output_type="pil", return_dict=True, clip_skip=None, use_graph=True, **unused):
+                 output_type="pil", return_dict=True, clip_skip=None, use_graph=True,
+                 ip_adapter_image=None, ip_adapter_image_embeds=None, **unused):
         if eta != 0.0:
             raise NotImplementedError("eta > 0")
         if output_type not in ("latent", "pt", "np", "pil"):
@@ -534,6 +659,8 @@ class AnimateDiffVideoToVideoPipeline(AnimateDiffPipeline):
             ehs = torch.cat([negative_prompt_embeds.to(prompt_embeds), prompt_embeds])
         else:
             ehs = prompt_embeds
+        ip_embeds = self.prepare_ip_adapter_image_embeds(ip_adapter_image, ip_adapter_image_embeds,
+                                                         B // num_videos_per_prompt, num_videos_per_prompt, do_cfg)
         self.scheduler.set_timesteps(num_inference_steps)
         ts, _ = self.get_timesteps(num_inference_steps, strength)
         if latents is None:
@@ -549,7 +676,7 @@ class AnimateDiffVideoToVideoPipeline(AnimateDiffPipeline):
             fl = self.dist.frames_local(num_frames)
             local = latents[:, :, self.dist.rank * fl:(self.dist.rank + 1) * fl]
         loop = DenoiseLoop(self.unet, self.scheduler, local, ehs, guidance_scale, timesteps=ts,
-                           use_graph=use_graph).prime()
+                           use_graph=use_graph, ip_embeds=ip_embeds).prime()
         out = loop.run()
         if self.dist is not None:
             out = self.dist.all_gather_frames(out)

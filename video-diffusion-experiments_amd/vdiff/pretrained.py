@@ -229,3 +229,96 @@ def load_scheduler(sched_dir):
     s = cls.from_config({k: v for k, v in cfg.items() if not k.startswith("_")})
     s.source_config = cfg
     return s
+
+
+# ---------------------------------------------------------------------------- IP-Adapter
+# An IP-Adapter checkpoint numbers its per-attention weights `ip_adapter.{id}.to_k_ip.weight` /
+# `.to_v_ip.weight` with id = 1, 3, 5, ...: diffusers walks the UNet's attention processors in
+# module order, counts every one, and the cross-attentions are the odd ones — motion modules
+# skipped.  For UNetMotionModel that order is the blocks below, each block's attentions[i].
+# transformer_blocks[j].attn2 in turn.  This table is the ONE place the order is written down
+# (UNetMotionModel.spatial_cross_attentions follows it); it restates diffusers'
+# _convert_ip_adapter_attn_to_diffusers and is not pinned by any file in this repository.
+IP_ADAPTER_BLOCK_ORDER = ("down_blocks", "up_blocks", "mid_block")
+IP_ADAPTER_WEIGHT_NAME = "ip-adapter_sd15.safetensors"
+
+
+def ip_adapter_key_ids(n_cross: int) -> list:
+    """The checkpoint ids of the n_cross spatial cross-attentions, in IP_ADAPTER_BLOCK_ORDER."""
+    return [2 * i + 1 for i in range(n_cross)]
+
+
+def read_ip_adapter(path, subfolder=None, weight_name=IP_ADAPTER_WEIGHT_NAME):
+    """(image_proj, ip_adapter): the two key groups of a LOCAL adapter file, prefixes stripped.
+    `.safetensors` holds flat `image_proj.*` / `ip_adapter.*` keys, `.bin` (torch.load with
+    weights_only=True) the two groups as nested dicts."""
+    if isinstance(path, (list, tuple)) or isinstance(weight_name, (list, tuple)):
+        raise NotImplementedError("a list of IP-Adapters (multiple image prompts) is not supported: load one")
+    if isinstance(path, dict):
+        sd = path
+    else:
+        f = _local_dir(path, "load_ip_adapter")
+        if subfolder:
+            f = f / subfolder
+        f = f / weight_name
+        if not f.exists():
+            raise FileNotFoundError(f"no {weight_name} in {f.parent} (local files only)")
+        if f.suffix == ".safetensors":
+            from safetensors.torch import load_file
+            sd = load_file(str(f))
+        elif f.suffix == ".bin":
+            sd = torch.load(str(f), map_location="cpu", weights_only=True)
+        else:
+            raise ValueError(f"{f.name}: an IP-Adapter file is .safetensors or .bin")
+    groups = {"image_proj": {}, "ip_adapter": {}}
+    for k, v in sd.items():
+        if k in groups and isinstance(v, dict):
+            groups[k].update(v)
+            continue
+        g, _, rest = k.partition(".")
+        if g not in groups:
+            raise KeyError(f"IP-Adapter checkpoint: key {k!r} is in neither the image_proj nor the ip_adapter group")
+        groups[g][rest] = v
+    return groups["image_proj"], groups["ip_adapter"]
+
+
+def check_ip_adapter_variant(image_proj: dict, ip_adapter: dict):
+    """Only the plain adapter (image_proj.proj + image_proj.norm, to_k_ip / to_v_ip) is built."""
+    if any(k == "latents" or k.startswith("latents.") for k in image_proj):
+        raise NotImplementedError("IP-Adapter Plus (image_proj.latents: the Resampler projection) is not supported")
+    if any(k.startswith("proj.0.") for k in image_proj):
+        raise NotImplementedError("IP-Adapter Full Face / FaceID (image_proj.proj.0.*: an MLP projection) is not supported")
+    if any("to_k_lora" in k or "to_q_lora" in k or "to_v_lora" in k or "to_out_lora" in k for k in ip_adapter):
+        raise NotImplementedError("IP-Adapter FaceID (ip_adapter.*.to_k_lora*: LoRA attention weights) is not supported")
+    want = {"proj.weight", "proj.bias", "norm.weight", "norm.bias"}
+    if set(image_proj) != want:
+        raise KeyError(f"IP-Adapter image_proj keys {sorted(image_proj)}: expected {sorted(want)}")
+
+
+def ip_adapter_kv_weights(ip_adapter: dict, n_cross: int) -> list:
+    """[(to_k_ip.weight, to_v_ip.weight)] per spatial cross-attention, by ip_adapter_key_ids."""
+    want = {f"{i}.to_{kv}_ip.weight" for i in ip_adapter_key_ids(n_cross) for kv in "kv"}
+    missing, unexpected = sorted(want - set(ip_adapter)), sorted(set(ip_adapter) - want)
+    if missing or unexpected:
+        raise KeyError(f"IP-Adapter ip_adapter keys do not fit {n_cross} cross-attentions: "
+                       f"missing={missing[:4]} unexpected={unexpected[:4]}")
+    return [(ip_adapter[f"{i}.to_k_ip.weight"], ip_adapter[f"{i}.to_v_ip.weight"]) for i in ip_adapter_key_ids(n_cross)]
+
+
+def load_image_encoder(enc_dir, device="cuda", variant=None):
+    """transformers' `image_encoder/` folder (config.json of a CLIPVisionConfig + model[.variant].
+    safetensors) -> vdiff.CLIPVisionModelWithProjection in bf16 on `device` (not prepared)."""
+    from safetensors.torch import load_file
+
+    from .models.clip import CLIPVisionModelWithProjection
+    d = _local_dir(enc_dir, "image_encoder")
+    cfg = read_json(d / "config.json")
+    cfg = cfg.get("vision_config", cfg) if "hidden_size" not in cfg else cfg
+    f = d / ("model" + (f".{variant}" if variant else "") + ".safetensors")
+    if not f.exists():
+        raise FileNotFoundError(f"no {f.name} in {d}")
+    with torch.device("meta"):
+        m = CLIPVisionModelWithProjection(cfg)
+    m = m.to_empty(device=device).to(dtype=torch.bfloat16)
+    m.load_state_dict({k: v.to(torch.bfloat16) for k, v in load_file(str(f)).items()}, strict=True)
+    return m.eval()
