@@ -502,8 +502,32 @@ int vd_block_transpose(const void* src, void* dst, int64_t nb, int64_t na, int64
  *   if y_f32) — residual adds, the ResnetBlock2D time-embedding broadcast, the sinusoidal
  *   positional embedding, repeat_interleave, channel concat into column slices;
  *   op 1: out[r] = silu(x[r]) (nn.SiLU).
+ *   Ops 2 and 3 are FreeU (diffusers' apply_freeu, run before each skip concat of up_blocks[0]
+ *   and [1]).  They ride on this entry point instead of a new symbol, as VD_CONV_PAD_END and
+ *   VD_ATTN_TAIL ride on theirs: the operands are the same bf16 rows with the same alignment
+ *   rules, and the set of exported symbols (vd_version 6) stays what it is.  The signature has
+ *   no float slot, so both read their scalar from DEVICE memory, inside the launch only (the
+ *   call stays graph-capturable and the value may change between replays): y points to one
+ *   fp32, 4-byte aligned, with y_f32 == 1 and ldy == 0 (anything else is VD_EINVAL).
+ *   op 2, VD_ROWS_FREEU_FILTER: diffusers' fourier_filter(x, threshold=1, scale=*y) on the rows
+ *   of n_img H x W images, H = y_period, W = y_div, rows = n_img * H * W.  threshold 1 scales
+ *   the four frequency bins k_h, k_w in {-1, 0} only, so per (image, channel) plane, with
+ *   th = 2 pi h / H and tw = 2 pi w / W,
+ *     out = x + (s - 1) / (H W) * (A + B cos th + C sin th + D cos tw + E sin tw
+ *                                    + P cos(th + tw) + Q sin(th + tw)),
+ *   A .. Q the plane's sums of x times the same seven factors.  One launch; fp32 sums in an
+ *   order fixed by (H, W) alone (never by n_img, the image's index or C: a frame-sharded call
+ *   matches the unsharded one bit for bit), no atomics; one rounding to bf16, of
+ *   fmaf((s - 1) / (H W), corr, x), so s == 1 returns x (a -0 may come back as +0: 0 * corr is
+ *   added to it).  out may be a column slice of a wider
+ *   buffer.  VD_EINVAL: H < 2 or W < 2 (the 2 x 2 box collapses), H + W > 4096, rows not a
+ *   multiple of H * W, x or y NULL, out == x.
+ *   op 3, VD_ROWS_SCALE: out[r][c] = bf16(x[r][c] * *y) over C columns; out == x is allowed
+ *   (FreeU's hidden_states[:, :C/2] *= b, on the column slice alone).  y_div and y_period are
+ *   not read.
  * vd_upsample_nearest2x: rows of n_img h x w images -> rows of their nearest x2 upsample
  *   (Upsample2D's F.interpolate(scale_factor=2.0, mode="nearest")). */
+enum { VD_ROWS_ADD = 0, VD_ROWS_SILU = 1, VD_ROWS_FREEU_FILTER = 2, VD_ROWS_SCALE = 3 };
 int vd_rows_eltwise(int32_t op, const void* x, int64_t ldx, const void* y, int64_t ldy, int32_t y_f32,
                     int64_t y_div, int64_t y_period, int64_t rows, int64_t C, void* out, int64_t ldo,
                     vd_stream_t stream);

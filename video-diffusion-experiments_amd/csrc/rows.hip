@@ -26,17 +26,22 @@ __device__ __forceinline__ void load8_any(const void* p, int is_f32, float* f) {
 
 // op 0: out[r] = (x ? x[r] : 0) + y[(r / y_div) % y_period]     (y bf16 or fp32)
 // op 1: out[r] = silu(x[r])
+// op 3: out[r] = x[r] * *y                                        (y one fp32 on the device)
 __global__ void rows_eltwise_kernel(int op, const bf16_t* x, int64_t ldx, const void* y, int64_t ldy, int y_f32,
                                     int64_t y_div, int64_t y_period, int64_t rows, int64_t C, bf16_t* out,
                                     int64_t ldo) {
   const int64_t cpr = C / 8;
   const int64_t total = rows * cpr;
+  const float g = op == VD_ROWS_SCALE ? *(const float*)y : 1.0f;
   for (int64_t i = (int64_t)blockIdx.x * NT + threadIdx.x; i < total; i += (int64_t)gridDim.x * NT) {
     const int64_t r = i / cpr;
     const int64_t c = (i - r * cpr) * 8;
     float v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (x) unpack8(*(const uint4*)(x + r * ldx + c), v);
-    if (op == 0) {
+    if (op == VD_ROWS_SCALE) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) v[j] *= g;
+    } else if (op == 0) {
       const int64_t yr = (r / y_div) % y_period;
       float w[8];
       load8_any(y_f32 ? (const void*)((const float*)y + yr * ldy + c) : (const void*)((const bf16_t*)y + yr * ldy + c),
@@ -65,6 +70,148 @@ __global__ void upsample2x_kernel(const bf16_t* x, int64_t ldx, int64_t n_img, i
   }
 }
 
+// op 2, FreeU's fourier_filter(threshold = 1): per (image, channel) plane of H x W pixels, with
+// th = 2 pi h / H and tw = 2 pi w / W,
+//   out = x + (s - 1) / (H W) * (A + B cos th + C sin th + D cos tw + E sin tw
+//                                  + P cos(th + tw) + Q sin(th + tw)),
+// A .. Q the plane's sums of x times the same seven factors (the four FFT bins k_h, k_w in
+// {-1, 0} that diffusers' 2 x 2 mask scales, written out; include/vdiff.h).
+// One workgroup per (image, slab of n8 8-channel chunks): thread t owns chunk t % n8 (a pixel
+// row's n8 * 16 bytes are contiguous over adjacent threads) and pixel lane t / n8 of FU_L, i.e.
+// pixels lane, lane + FU_L, ...  The summation order of a plane is a function of (H, W) alone:
+// a lane adds its pixels in ascending order, the FU_L lanes are combined as a balanced tree over
+// the lane index bits, lowest first — wave shuffles for the bits inside a wave, LDS for the
+// bits that select the wave — and a + b == b + a makes the butterfly's two sides equal.  So the
+// slab width n8 (chosen from the grid size, i.e. from n_img) and the image's index change no bit.
+// KEEP: planes of <= FU_L * FU_KEEP pixels (every UNet shape) stay in registers between the two
+// passes; larger planes are read again.
+constexpr int FU_L = 32, FU_KEEP = 8, FU_NS = 7;
+constexpr int FU_RED = 4 * 8 * FU_NS * 8;  // floats: [wave][chunk][sum][channel]
+
+struct FuTw {
+  float ch, sh, cw, sw, cp, sp;
+};
+__device__ __forceinline__ FuTw fu_twiddle(const float2* tw, int p, int H, int W) {
+  const int h = p / W, w = p - h * W;
+  const float2 a = tw[h], b = tw[H + w];
+  return {a.x, a.y, b.x, b.y, a.x * b.x - a.y * b.y, a.y * b.x + a.x * b.y};
+}
+__device__ __forceinline__ void fu_accum(float (&acc)[FU_NS][8], const uint4& u, const FuTw& t) {
+  float f[8];
+  unpack8(u, f);
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    acc[0][e] += f[e];
+    acc[1][e] = fmaf(f[e], t.ch, acc[1][e]);
+    acc[2][e] = fmaf(f[e], t.sh, acc[2][e]);
+    acc[3][e] = fmaf(f[e], t.cw, acc[3][e]);
+    acc[4][e] = fmaf(f[e], t.sw, acc[4][e]);
+    acc[5][e] = fmaf(f[e], t.cp, acc[5][e]);
+    acc[6][e] = fmaf(f[e], t.sp, acc[6][e]);
+  }
+}
+__device__ __forceinline__ uint4 fu_apply(const float (&acc)[FU_NS][8], const uint4& u, const FuTw& t, float k) {
+  float f[8];
+  unpack8(u, f);
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    float c = fmaf(acc[1][e], t.ch, acc[0][e]);
+    c = fmaf(acc[2][e], t.sh, c);
+    c = fmaf(acc[3][e], t.cw, c);
+    c = fmaf(acc[4][e], t.sw, c);
+    c = fmaf(acc[5][e], t.cp, c);
+    c = fmaf(acc[6][e], t.sp, c);
+    f[e] = fmaf(k, c, f[e]);
+  }
+  return pack8(f);
+}
+
+template <bool KEEP>
+__global__ __launch_bounds__(NT) void freeu_filter_kernel(const bf16_t* x, int64_t ldx, const float* s_dev, int H,
+                                                          int W, int n8, int nslab, bf16_t* out, int64_t ldo) {
+  extern __shared__ __attribute__((aligned(16))) float fu_smem[];
+  float* red = fu_smem;                      // the waves' partial sums
+  float2* tw = (float2*)(fu_smem + FU_RED);  // (cos, sin) of 2 pi i / H, then of 2 pi j / W
+  const int t = threadIdx.x, pix = H * W;
+  for (int i = t; i < H + W; i += blockDim.x) {
+    // sin / cos of pi * a, a in [0, 2): no large angle is ever reduced
+    const float a = i < H ? 2.0f * (float)i / (float)H : 2.0f * (float)(i - H) / (float)W;
+    float sn, cs;
+    sincospif(a, &sn, &cs);
+    tw[i] = make_float2(cs, sn);
+  }
+  __syncthreads();
+  const int c8 = t % n8, lane = t / n8;
+  const bool act = lane < FU_L;  // n8 == 1 runs one wave, its upper half idle
+  const int img = blockIdx.x / nslab, slab = blockIdx.x % nslab;
+  const int64_t c = ((int64_t)slab * n8 + c8) * 8;
+  const bf16_t* xp = x + (int64_t)img * pix * ldx + c;
+  bf16_t* dst = out + (int64_t)img * pix * ldo + c;
+
+  float acc[FU_NS][8];
+#pragma unroll
+  for (int j = 0; j < FU_NS; ++j)
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc[j][e] = 0.f;
+  uint4 v[KEEP ? FU_KEEP : 1];
+  if (KEEP) {
+#pragma unroll
+    for (int k = 0; k < FU_KEEP; ++k) {
+      const int p = lane + k * FU_L;
+      v[k] = make_uint4(0, 0, 0, 0);
+      if (act && p < pix) v[k] = *(const uint4*)(xp + (int64_t)p * ldx);
+    }
+#pragma unroll
+    for (int k = 0; k < FU_KEEP; ++k) {
+      const int p = lane + k * FU_L;
+      if (act && p < pix) fu_accum(acc, v[k], fu_twiddle(tw, p, H, W));
+    }
+  } else if (act) {
+    for (int p = lane; p < pix; p += FU_L) fu_accum(acc, *(const uint4*)(xp + (int64_t)p * ldx), fu_twiddle(tw, p, H, W));
+  }
+
+  // lane bits inside the wave: threads t and t ^ o hold the same chunk, lanes that differ in one bit
+  for (int o = n8; o < 64; o <<= 1) {
+#pragma unroll
+    for (int j = 0; j < FU_NS; ++j)
+#pragma unroll
+      for (int e = 0; e < 8; ++e) acc[j][e] += __shfl_xor(acc[j][e], o, 64);
+  }
+  // lane bits that select the wave (n8 = 4: two waves, n8 = 8: four)
+  const int nw = blockDim.x / 64;
+  if (nw > 1) {
+    const int wv = t / 64;
+    if ((t & 63) < n8) {
+#pragma unroll
+      for (int j = 0; j < FU_NS; ++j)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) red[((wv * n8 + c8) * FU_NS + j) * 8 + e] = acc[j][e];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < FU_NS; ++j)
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const int q = (c8 * FU_NS + j) * 8 + e, ws = n8 * FU_NS * 8;
+        const float a = red[q] + red[ws + q];
+        acc[j][e] = nw == 2 ? a : a + (red[2 * ws + q] + red[3 * ws + q]);
+      }
+  }
+  if (!act) return;
+
+  const float k = (*s_dev - 1.0f) / (float)pix;
+  if (KEEP) {
+#pragma unroll
+    for (int kk = 0; kk < FU_KEEP; ++kk) {
+      const int p = lane + kk * FU_L;
+      if (p < pix) *(uint4*)(dst + (int64_t)p * ldo) = fu_apply(acc, v[kk], fu_twiddle(tw, p, H, W), k);
+    }
+  } else {
+    for (int p = lane; p < pix; p += FU_L)
+      *(uint4*)(dst + (int64_t)p * ldo) = fu_apply(acc, *(const uint4*)(xp + (int64_t)p * ldx), fu_twiddle(tw, p, H, W), k);
+  }
+}
+
 unsigned grid_for(int64_t total) {
   const int64_t b = (total + NT - 1) / NT;
   return (unsigned)(b < 16384 ? (b > 0 ? b : 1) : 16384);
@@ -77,13 +224,37 @@ inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 extern "C" int vd_rows_eltwise(int32_t op, const void* x, int64_t ldx, const void* y, int64_t ldy, int32_t y_f32,
                                int64_t y_div, int64_t y_period, int64_t rows, int64_t C, void* out, int64_t ldo,
                                vd_stream_t stream) {
-  VD_CHECK_ARG((op == 0 || op == 1) && out && rows > 0 && C > 0 && C % 8 == 0 && ldo % 8 == 0 && ldo >= C);
+  VD_CHECK_ARG(op >= VD_ROWS_ADD && op <= VD_ROWS_SCALE && out && rows > 0 && C > 0 && C % 8 == 0 && ldo % 8 == 0 &&
+               ldo >= C);
   VD_CHECK_ARG(al16(out));
   if (x) VD_CHECK_ARG(al16(x) && ldx % 8 == 0 && ldx >= C);
   if (op == 0) {
     VD_CHECK_ARG(y && al16(y) && ldy >= C && ldy % (y_f32 ? 4 : 8) == 0 && y_div > 0 && y_period > 0);
   } else {
     VD_CHECK_ARG(x != nullptr);
+  }
+  if (op == VD_ROWS_FREEU_FILTER || op == VD_ROWS_SCALE)  // the scalar: one fp32 on the device
+    VD_CHECK_ARG(y && ((uintptr_t)y & 3) == 0 && y_f32 == 1 && ldy == 0);
+  if (op == VD_ROWS_FREEU_FILTER) {
+    const int64_t H = y_period, W = y_div;
+    VD_CHECK_ARG(H >= 2 && W >= 2 && H + W <= 4096 && rows % (H * W) == 0 && out != x);
+    const int64_t n_img = rows / (H * W), nchunk = C / 8;
+    // the widest slab (one 128-byte line per pixel row at n8 = 8) that still gives every CU two
+    // workgroups; a grid that cannot reach that runs one chunk per workgroup
+    int n8 = 1;
+    for (int w : {8, 4, 2})
+      if (nchunk % w == 0 && n_img * (nchunk / w) >= 2 * 256) {
+        n8 = w;
+        break;
+      }
+    const int64_t nslab = nchunk / n8, grid = n_img * nslab;
+    VD_CHECK_ARG(grid <= 0x7fffffff);
+    const unsigned nt = n8 == 1 ? 64 : n8 * FU_L;
+    const size_t lds = (FU_RED + 2 * (size_t)(H + W)) * sizeof(float);
+    auto kern = H * W <= FU_L * FU_KEEP ? freeu_filter_kernel<true> : freeu_filter_kernel<false>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(nt), lds, (hipStream_t)stream, (const bf16_t*)x, ldx,
+                       (const float*)y, (int)H, (int)W, n8, (int)nslab, (bf16_t*)out, ldo);
+    return vd_launch_status();
   }
   hipLaunchKernelGGL(rows_eltwise_kernel, dim3(grid_for(rows * (C / 8))), dim3(NT), 0, (hipStream_t)stream, op,
                      (const bf16_t*)x, ldx, y, ldy, y_f32, y_div, y_period, rows, C, (bf16_t*)out, ldo);

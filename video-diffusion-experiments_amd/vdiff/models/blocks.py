@@ -518,6 +518,8 @@ class _MotionBlockBase(nn.Module):
                 x = res0[0] if attns is not None else Act(torch.cat([res0[1].t, res0[1].t]), res0[0].n, res0[0].h,
                                                            res0[0].w)
             else:
+                if skip is not None:  # an up block: FreeU, when enabled, before the (virtual) concat
+                    x, skip = self.freeu_rows(x, skip)
                 x = res.run(x, ctx, skip=skip)
             if attns is not None:
                 x = attns[i].run(x, ctx, half=res0[1] if dup else None)
@@ -530,7 +532,8 @@ class _MotionBlockBase(nn.Module):
         outs = ()
         for i, res in enumerate(self.resnets):
             if res_tuple is not None:
-                h = concat_channels(h, res_tuple[-1])
+                h, skip = self.freeu_maps(h, res_tuple[-1])
+                h = concat_channels(h, skip)
                 res_tuple = res_tuple[:-1]
             h = res(h, temb)
             if attns is not None:
@@ -603,6 +606,54 @@ class CrossAttnUpBlockMotion(_MotionBlockBase):
             for _ in range(n)])
         self.upsamplers = (nn.ModuleList([Upsample2D(out_channels, out_channels)])
                            if add_upsample else None)
+        # FreeU (diffusers' FreeUMixin / apply_freeu): the block's place in up_blocks and the four
+        # factors UNetMotionModel.enable_freeu sets on every up block; only blocks 0 and 1 use them
+        self.resolution_idx = None
+        self.s1 = self.s2 = self.b1 = self.b2 = None
+        self._freeu = None  # fp32 [s, b] on the device while active (the kernels read it there)
+
+    @property
+    def freeu_active(self) -> bool:
+        return self.resolution_idx in (0, 1) and None not in (self.s1, self.s2, self.b1, self.b2)
+
+    def prepare(self):
+        """(Re-)make the device operand of an active FreeU block: [s1, b1] or [s2, b2]."""
+        self._freeu = None
+        dev = next(self.parameters()).device
+        if self.freeu_active and dev.type == "cuda":
+            s, b = (self.s1, self.b1) if self.resolution_idx == 0 else (self.s2, self.b2)
+            self._freeu = torch.tensor([float(s), float(b)], dtype=torch.float32, device=dev)
+
+    def _freeu_operands(self, hidden_channels):
+        if not self.freeu_active:
+            return None
+        if (hidden_channels // 2) % 8 or hidden_channels % 2:
+            raise NotImplementedError(f"FreeU: half of the {hidden_channels} hidden channels is not a multiple of 8 "
+                                      "(the backbone scale runs on 16-byte column chunks)")
+        if self._freeu is None:
+            self.prepare()
+        return self._freeu[0:1], self._freeu[1:2]
+
+    def freeu_rows(self, x: Act, skip: Act):
+        """apply_freeu on the fast path's rows, before resnets[i] reads (x, skip) as its two
+        sources: x's first half of the channels scaled in place (x is read by that resnet alone),
+        the skip filtered into a fresh buffer."""
+        fu = self._freeu_operands(x.c)
+        if fu is None:
+            return x, skip
+        ops.scale_rows_(x.t[:, :x.c // 2], fu[1])
+        return x, Act(ops.freeu_filter(skip.t, skip.n, skip.h, skip.w, fu[0]), skip.n, skip.h, skip.w)
+
+    def freeu_maps(self, h, res):
+        """apply_freeu on the module path's diffusers-layout feature maps (N, C, H, W)."""
+        fu = self._freeu_operands(h.shape[1])
+        if fu is None:
+            return h, res
+        hr = fmap_rows(h)
+        ops.scale_rows_(hr[:, :h.shape[1] // 2], fu[1])
+        n, _, hh, ww = res.shape
+        return rows_fmap(hr, tuple(h.shape)), rows_fmap(ops.freeu_filter(fmap_rows(res), n, hh, ww, fu[0]),
+                                                         tuple(res.shape))
 
     def run(self, x, ctx, skips):
         x, _ = self._run_layers(x, ctx, skips_in=skips)

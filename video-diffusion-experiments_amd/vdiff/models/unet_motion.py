@@ -73,6 +73,7 @@ class UNetMotionModel(nn.Module):
                 blk = CrossAttnUpBlockMotion(ins, out_ch, tdim, heads, cross, mheads, up, g, eps, mlen)
             else:
                 blk = UpBlockMotion(ins, out_ch, tdim, mheads, up, g, eps, mlen)
+            blk.resolution_idx = len(self.up_blocks)
             self.up_blocks.append(blk)
         self.mid_block = UNetMidBlockCrossAttnMotion(boc[-1], tdim, heads, cross, mheads, g, eps, mlen,
                                                      use_motion=cfg.get("use_motion_mid_block", True))
@@ -162,6 +163,22 @@ class UNetMotionModel(nn.Module):
     def unload_ip_adapter(self):
         for a in self.spatial_cross_attentions():
             a.remove_ip_adapter()
+
+    # ------------------------------------------------------------------ FreeU
+    def enable_freeu(self, s1, s2, b1, b2):
+        """diffusers' FreeUMixin.enable_freeu: s1 / b1 act in up_blocks[0], s2 / b2 in
+        up_blocks[1] — before each skip concat the skip's four lowest frequency bins are scaled by
+        s and the first half of the backbone channels by b (vd_rows_eltwise ops 2 and 3).  The
+        attributes are set on every up block, as diffusers does; a DenoiseLoop built afterwards
+        captures the extra launches, one built before keeps running without them."""
+        for blk in self.up_blocks:
+            blk.s1, blk.s2, blk.b1, blk.b2 = s1, s2, b1, b2
+            blk.prepare()
+
+    def disable_freeu(self):
+        for blk in self.up_blocks:
+            blk.s1 = blk.s2 = blk.b1 = blk.b2 = None
+            blk.prepare()
 
     def forward_rows(self, x_rows, h, w, ctx: Ctx):
         """Packed NHWC input rows [batch*frames*h*w, 8] -> eps rows fp32 [..., out_channels]."""

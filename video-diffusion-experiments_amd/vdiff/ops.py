@@ -787,6 +787,38 @@ def silu_rows(x, out=None):
     return out
 
 
+ROWS_FREEU_FILTER, ROWS_SCALE = 2, 3  # VD_ROWS_FREEU_FILTER, VD_ROWS_SCALE
+
+
+def _dev_scalar(t, what):
+    """One fp32 on the device: the operand ops 2 and 3 of vd_rows_eltwise read inside the launch."""
+    if t.dtype != torch.float32 or t.numel() != 1:
+        raise ValueError(f"{what}: expected one fp32 element on the device, got {t.dtype} x {t.numel()}")
+
+
+def freeu_filter(x, n_img, h, w, s_dev, out=None):
+    """diffusers' fourier_filter(x, threshold=1, scale=s) (FreeU) on the bf16 NHWC rows of n_img
+    h x w images, s = s_dev[0] read on the device; `out` may be a column slice, never x itself."""
+    _dev(x, s_dev, out)
+    _dev_scalar(s_dev, "freeu_filter s_dev")
+    if x.shape[0] != n_img * h * w:
+        raise ValueError(f"freeu_filter: {x.shape[0]} rows are not {n_img} images of {h} x {w}")
+    if out is None:
+        out = torch.empty(x.shape[0], x.shape[1], device=x.device, dtype=BF16)
+    check(lib().vd_rows_eltwise(ROWS_FREEU_FILTER, _p(x), _rows(x), _p(s_dev), 0, 1, w, h, x.shape[0], x.shape[1],
+                                _p(out), _rows(out), _stream()), "vd_rows_eltwise(freeu_filter)")
+    return out
+
+
+def scale_rows_(x_slice, g_dev):
+    """x_slice *= g_dev[0] in place over bf16 rows (a column slice moves only its own bytes)."""
+    _dev(x_slice, g_dev)
+    _dev_scalar(g_dev, "scale_rows_ g_dev")
+    check(lib().vd_rows_eltwise(ROWS_SCALE, _p(x_slice), _rows(x_slice), _p(g_dev), 0, 1, 1, 1, x_slice.shape[0],
+                                x_slice.shape[1], _p(x_slice), _rows(x_slice), _stream()), "vd_rows_eltwise(scale)")
+    return x_slice
+
+
 def upsample2x_rows(x, n_img, h, w, out=None):
     _dev(x, out)
     if out is None:

@@ -133,6 +133,9 @@ class DenoiseLoop:
         self.x_in2 = ops.pack_latents(self.lat, dup=self.ncfg, cpad=CIN_PAD, in_div=self.in_div0)
         self.x_in = self.x_in2[:self.Bu * self.F * self.H * self.W]
         self.kv_cache = {}
+        # the FreeU scalars the step's launches (and the graph) read: kept alive for this loop's
+        # life, whatever enable_freeu / disable_freeu does to the blocks afterwards
+        self.freeu_operands = [b._freeu for b in unet.up_blocks]
         # conv_in + down_blocks[0].resnets[0] once for both CFG halves (UNetMotionModel.forward_rows)
         self.cfg_dedup = True
         self.use_graph = use_graph
@@ -320,6 +323,14 @@ class AnimateDiffPipeline:
 
     def to(self, *a, **k):
         return self
+
+    def enable_freeu(self, s1: float, s2: float, b1: float, b2: float):
+        """diffusers' FreeUMixin.enable_freeu (UNetMotionModel.enable_freeu); the next __call__
+        builds its DenoiseLoop, and so its graph, with it."""
+        self.unet.enable_freeu(s1=s1, s2=s2, b1=b1, b2=b2)
+
+    def disable_freeu(self):
+        self.unet.disable_freeu()
 
     # ------------------------------------------------------------------ IP-Adapter
     def load_ip_adapter(self, pretrained_model_name_or_path_or_dict, subfolder=None,
