@@ -286,7 +286,7 @@ int vd_attention_f32(const void* q, int64_t ldq, const void* k, int64_t ldk, con
  * from 4 key tiles, flash32 below; d = 80 -> flash80 from 4 key tiles (round 6); other d -> the
  * 16x16x32 flash kernel), 1 = the 16x16x32 flash kernel for any d, 2 = flash32 (d = 40),
  * 3 = flash40 / flash80 wherever they apply (d = 40 / 80, >= 2 key tiles); a kernel that does not
- * take the shape falls through to the next one down.  All of
+ * take the shape falls through to the next one down (vd_attention_plan names the one that runs).  All of
  * them compute softmax(q k^T * scale) v; flash40 is bit-identical to flash32 (the parity tests
  * run each).  out_f32 as vd_attention_f32.
  * VD_ATTN_CAUSAL OR-ed into kernel: query i attends to keys j <= i only (the CLIP text encoder's
@@ -310,6 +310,29 @@ enum { VD_ATTN_TAIL_SHIFT = 16, VD_ATTN_TAIL_MASK = 0x7f0000 };
 int vd_attention_ex(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
                     void* o, int64_t ldo, int64_t batch, int32_t heads, int64_t sq, int64_t skv, int32_t d,
                     int64_t kv_div, float scale, int32_t out_f32, int32_t kernel, vd_stream_t stream);
+/* The plan vd_attention_ex would run for these sizes, this output address (read as a number,
+ * never dereferenced) and stride, and this kernel word (VD_ATTN_CAUSAL / VD_ATTN_TAIL included):
+ * host only, no launch, no device needed.  Returns what the call would return before it
+ * launches, as far as it depends on these arguments (the q / k / v pointers and strides are
+ * not asked about): VD_OK, VD_EINVAL or VD_EUNSUPPORTED, with every output 0 unless VD_OK.
+ *   *family      the kernel family, VD_ATTN_K_* — where a forced kernel did not take the shape,
+ *                the one it fell through to
+ *   *qblk        VD_ATTN_K_FLASH: 16-query blocks per wave, 2 or 4 (a workgroup holds 64 * qblk
+ *                queries); 0 for the other families
+ *   *unit_scale  flash32 / flash40 / flash80: 1 when scale * log2(e) == 1 in fp32 and the
+ *                instance without the per-score multiply runs; 0 for the other families
+ *   *grid        workgroups of the (first) launch
+ *   *exact_grid  VD_ATTN_K_FLASH40: workgroups of flash32's exact pass launched after it; else 0 */
+enum {
+  VD_ATTN_K_FLASH = 1,    /* the 16x16x32 flash kernel (plain, causal, tailed) */
+  VD_ATTN_K_FLASH32 = 2,  /* d = 40 */
+  VD_ATTN_K_FLASH40 = 3,  /* d = 40, >= 2 key tiles */
+  VD_ATTN_K_FLASH80 = 4,  /* d = 80, >= 2 key tiles */
+  VD_ATTN_K_FLASH512 = 5  /* d = 512 */
+};
+int vd_attention_plan(const void* o, int64_t ldo, int64_t batch, int32_t heads, int64_t sq, int64_t skv, int32_t d,
+                      int64_t kv_div, float scale, int32_t out_f32, int32_t kernel, int32_t* family, int32_t* qblk,
+                      int32_t* unit_scale, int64_t* grid, int64_t* exact_grid);
 
 /* Temporal (motion-module) self-attention over frames (a9): token (b, f, p) is
  * row (b*frames + f)*positions + p of q/k/v/o (the NHWC layout, no permute);

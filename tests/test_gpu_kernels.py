@@ -921,6 +921,30 @@ def attn_path(request, cuda):
     return request.param
 
 
+def forced_family(kernel, d):
+    """The family a forced kernel names at head width d: flash40 / flash80 (d = 40 / 80) for
+    "flash40", flash32 (d = 40) for "flash32"; the 16x16x32 kernel for "v1" and wherever the named
+    kernel has no instance at that width."""
+    if kernel == "flash40" and d in (40, 80):
+        return "flash40" if d == 40 else "flash80"
+    return "flash32" if kernel == "flash32" and d == 40 else "flash"
+
+
+def forced_attention(kernel, q, k, v, batch, heads, sq, skv, d, **kw):
+    """ops.attention with a forced kernel, once the plan confirms that the named family (not one
+    it fell through to) is what runs at this shape."""
+    family = ops.attention_plan(q, k, v, batch, heads, sq, skv, d, kernel=kernel, **kw).family
+    assert family == forced_family(kernel, d), f"kernel={kernel} d={d} sq={sq} skv={skv} runs {family}"
+    return ops.attention(q, k, v, batch, heads, sq, skv, d, kernel=kernel, **kw)
+
+
+def flash40_skv(kernel, skv):
+    """flash40 takes a shape from two 64-key tiles.  Below that a forced flash40 ran flash32 (which
+    the "flash32" parameter covers at the same shape), so the "flash40" parameter moves such a case
+    to skv = 128, the smallest flash40 takes."""
+    return 128 if kernel == "flash40" and skv < 128 else skv
+
+
 @pytest.mark.parametrize("d", [32, 40, 64, 80, 128, 160])
 @pytest.mark.parametrize("sq", [64, 300, 1024])
 def test_flash_attention_self(cuda, d, sq):
@@ -961,10 +985,11 @@ def test_flash_attention_d40_paths(attn_path, sq, skv):
     keys past skv), fused-QKV strides for self and separate K/V otherwise."""
     torch.manual_seed(11)
     batch, heads, d = 2, 8, 40
+    skv = flash40_skv(attn_path, skv)
     C = heads * d
     q = rnd(batch * sq, 3 * C, std=1.5)[:, :C]
     kv = rnd(batch * skv, 2 * C, std=1.5)
-    got = ops.attention(q, kv[:, :C], kv[:, C:], batch, heads, sq, skv, d, kernel=attn_path)
+    got = forced_attention(attn_path, q, kv[:, :C], kv[:, C:], batch, heads, sq, skv, d)
     close_bf16(got, sdpa_ref(q, kv[:, :C], kv[:, C:], batch, heads, sq, skv, d))
 
 
@@ -1001,7 +1026,7 @@ def _deferred_max_case(kind, sq=256, skv=640, d=40):
 def test_flash_attention_deferred_max(attn_path, kind):
     q, k, v = _deferred_max_case(kind)
     sq, skv, d = q.shape[0], k.shape[0], q.shape[1]
-    got = ops.attention(q, k, v, 1, 1, sq, skv, d, kernel=attn_path)
+    got = forced_attention(attn_path, q, k, v, 1, 1, sq, skv, d)
     assert torch.isfinite(got.float()).all()
     # O is a convex combination of V rows and P is rounded to bf16 (relative 2^-9) before
     # PV, so the absolute error scales with |V|, not |O| (these cases concentrate the
@@ -1017,7 +1042,7 @@ def test_flash_attention_deferred_max_unit_scale(attn_path, kind):
     q, k, v = _deferred_max_case(kind)
     sq, skv, d = q.shape[0], k.shape[0], q.shape[1]
     q = bf(q.float() * d ** -0.5 * math.log2(math.e))  # scores in log2 units
-    got = ops.attention(q, k, v, 1, 1, sq, skv, d, scale=1.0 / math.log2(math.e), kernel=attn_path)
+    got = forced_attention(attn_path, q, k, v, 1, 1, sq, skv, d, scale=1.0 / math.log2(math.e))
     assert torch.isfinite(got.float()).all()
     want = sdpa_ref(q, k, v, 1, 1, sq, skv, d, scale=1.0 / math.log2(math.e))
     close_bf16(got, want, abs_frac=2e-3 * v.float().abs().max().item() / want.abs().max().item())
@@ -1036,7 +1061,7 @@ def test_flash80_deferred_max(cuda, kind, unit):
     if unit:
         q = bf(q.float() * d ** -0.5 * math.log2(math.e))
         sc = 1.0 / math.log2(math.e)
-    got = ops.attention(q, k, v, 1, 1, sq, skv, d, scale=sc, kernel="flash40")
+    got = forced_attention("flash40", q, k, v, 1, 1, sq, skv, d, scale=sc)
     assert torch.isfinite(got.float()).all()
     want = sdpa_ref(q, k, v, 1, 1, sq, skv, d, scale=sc)
     close_bf16(got, want, abs_frac=2e-3 * v.float().abs().max().item() / want.abs().max().item())
@@ -1056,7 +1081,7 @@ def test_flash80_matches_fp64(cuda, sq, skv, batch, kv_div):
     q = bf(q.float() * d ** -0.5 * math.log2(math.e))
     kv = rnd(batch // kv_div * skv, 2 * C, std=1.5)
     sc = 1.0 / math.log2(math.e)
-    got = ops.attention(q, kv[:, :C], kv[:, C:], batch, heads, sq, skv, d, kv_div=kv_div, scale=sc, kernel="flash40")
+    got = forced_attention("flash40", q, kv[:, :C], kv[:, C:], batch, heads, sq, skv, d, kv_div=kv_div, scale=sc)
     close_bf16(got, sdpa_ref(q, kv[:, :C], kv[:, C:], batch, heads, sq, skv, d, kv_div=kv_div, scale=sc))
     if skv >= 256:
         auto = ops.attention(q, kv[:, :C], kv[:, C:], batch, heads, sq, skv, d, kv_div=kv_div, scale=sc)
@@ -1088,11 +1113,13 @@ def test_attention_fp32_out_north_star_tolerance(attn_path, d, sq, skv, batch, k
     torch.manual_seed(d + sq)
     heads = 2
     C = heads * d
+    if d == 40:
+        skv = flash40_skv(attn_path, skv)
     q = bf(torch.randint(-1, 2, (batch * sq, C), device="cuda").float())
     k = bf(torch.randint(-1, 2, (batch // kv_div * skv, C), device="cuda").float())
     v = rnd(batch // kv_div * skv, C)
-    got = ops.attention(q, k, v, batch, heads, sq, skv, d, kv_div=kv_div, scale=1.0 / math.log2(math.e), out_f32=True,
-                        kernel=attn_path)
+    got = forced_attention(attn_path, q, k, v, batch, heads, sq, skv, d, kv_div=kv_div, scale=1.0 / math.log2(math.e),
+                           out_f32=True)
     assert got.dtype == torch.float32
     qd = q.double().reshape(batch, sq, heads, d).transpose(1, 2)
     kd = k.double().reshape(batch // kv_div, skv, heads, d).transpose(1, 2).repeat_interleave(kv_div, 0)
@@ -1106,8 +1133,8 @@ def test_attention_fp32_out_north_star_tolerance(attn_path, d, sq, skv, batch, k
 
 
 def _flash40_vs_flash32(q, k, v, batch, heads, sq, skv, d, kv_div=1, scale=None, out_f32=False):
-    a = ops.attention(q, k, v, batch, heads, sq, skv, d, kv_div=kv_div, scale=scale, out_f32=out_f32, kernel="flash40")
-    b = ops.attention(q, k, v, batch, heads, sq, skv, d, kv_div=kv_div, scale=scale, out_f32=out_f32, kernel="flash32")
+    a = forced_attention("flash40", q, k, v, batch, heads, sq, skv, d, kv_div=kv_div, scale=scale, out_f32=out_f32)
+    b = forced_attention("flash32", q, k, v, batch, heads, sq, skv, d, kv_div=kv_div, scale=scale, out_f32=out_f32)
     return a, b
 
 
@@ -1166,11 +1193,11 @@ def test_attention_d40_real_valued_north_star_tolerance(attn_path, sq, skv, batc
     torch.manual_seed(sq + skv)
     heads, d = 2, 40
     C = heads * d
+    skv = flash40_skv(attn_path, skv)
     q = bf(torch.randn(batch * sq, C, device="cuda") * 1.5 * d ** -0.5 * math.log2(math.e))
     k = bf(torch.randn(batch * skv, C, device="cuda") * 1.5)
     v = bf(torch.randn(batch * skv, C, device="cuda") * 1.5)
-    got = ops.attention(q, k, v, batch, heads, sq, skv, d, scale=1.0 / math.log2(math.e), out_f32=True,
-                        kernel=attn_path)
+    got = forced_attention(attn_path, q, k, v, batch, heads, sq, skv, d, scale=1.0 / math.log2(math.e), out_f32=True)
     qd = q.double().reshape(batch, sq, heads, d).transpose(1, 2)
     kd = k.double().reshape(batch, skv, heads, d).transpose(1, 2)
     vd = v.double().reshape(batch, skv, heads, d).transpose(1, 2)

@@ -64,6 +64,7 @@ COVERAGE = {
     "vd_attention": ("test_attention_abi_entry_points",),
     "vd_attention_f32": ("test_attention_abi_entry_points",),
     "vd_attention_ex": ("test_attention",),
+    "vd_attention_plan": "no launch: a plan query",
     "vd_temporal_attention": ("test_temporal_attention",),
     "vd_temporal_attention_valu": ("test_temporal_attention",),
     "vd_temporal_attention_kv": ("test_temporal_attention_kv",),
@@ -813,18 +814,23 @@ def flash512_ref(q, k, v, batch, sq, skv, kv_div):
 ATTN_SHAPES = [(200, 333), (300, 77), (64, 1), (130, 130)]
 
 
-def attn_kernels(d, skv):
-    """The kernels to ask for: every d = 40 kernel; flash40 / flash80 only where their launch
-    condition on skv (two 64-key tiles) holds — elsewhere the request falls through to another."""
-    if d == 40:
-        return ["v1", "flash32"] + (["flash40"] if skv >= 128 else [])
-    if d == 80:
-        return ["auto"] + (["flash40"] if skv >= 128 else [])
-    return ["auto"]
+# the family a forced kernel names at a head width that has more than one kernel
+ATTN_FORCED = {("v1", 40): "flash", ("flash32", 40): "flash32", ("flash40", 40): "flash40", ("flash40", 80): "flash80"}
+
+
+def attn_kernels(d, sq, skv):
+    """The kernels to ask for: at d = 40 / 80 every forced kernel whose family the plan
+    (ops.attention_plan: host only) says runs this shape on a dense, aligned output — elsewhere the
+    request falls through to another kernel of the list; "auto" where there is one kernel."""
+    names = {40: ["v1", "flash32", "flash40"], 80: ["auto", "flash40"]}.get(d, ["auto"])
+    def runs(n):
+        return ops.attention_plan(None, None, None, 2, 2, sq, skv, d, kernel=n).family == ATTN_FORCED[n, d]
+
+    return [n for n in names if n == "auto" or runs(n)]
 
 
 ATTN_CASES = [(d, sq, skv, kern) for d in (32, 40, 64, 80, 128, 160, 512) for sq, skv in ATTN_SHAPES
-              for kern in attn_kernels(d, skv)]
+              for kern in attn_kernels(d, sq, skv)]
 
 
 @pytest.mark.parametrize("slack", SLACKS)
@@ -837,7 +843,9 @@ def test_attention(cuda, slack, out_f32, d, sq, skv, kern):
     bf16 output on N(0, 1.5^2) data against fp64 SDPA; fp32 output on integer scores at the unit
     scale against fp64 at rtol 1e-3 / atol 1e-4 (d = 512: its own restatement and bounds).  `out`
     is a slack-column view (the odd slack: ldo % 8 == 4, except for d = 512's bf16 output, whose
-    launcher refuses an ldo that is no multiple of 8: it keeps 8)."""
+    launcher refuses an ldo that is no multiple of 8: it keeps 8).  A forced kernel runs its own
+    family (the plan says so) unless `out`'s rows are not 16-byte ones, which only the 16x16x32
+    kernel stores: that fall-through is framed like any other call."""
     heads = 1 if d == 512 else 2
     C = heads * d
     self_attn = sq == skv
@@ -865,7 +873,12 @@ def test_attention(cuda, slack, out_f32, d, sq, skv, kern):
             q, kv = mk.rows(qf, "q"), mk.rows(kvf, "kv")
             k, v = kv[:, :C], kv[:, C:]
         out = mk.out((batch * sq, C), F32 if out_f32 else BF, unaligned=out_f32 or d != 512)
-        ops.attention(q, k, v, batch, heads, sq, skv, d, kv_div=kv_div, scale=scale, out=out, out_f32=out_f32, kernel=kern)
+        kw = dict(kv_div=kv_div, scale=scale, out=out, out_f32=out_f32, kernel=kern)
+        if kern != "auto":
+            rows16 = out.data_ptr() % 16 == 0 and out.stride(0) * out.element_size() % 16 == 0
+            assert ops.attention_plan(q, k, v, batch, heads, sq, skv, d, **kw).family == \
+                (ATTN_FORCED[kern, d] if rows16 else "flash")
+        ops.attention(q, k, v, batch, heads, sq, skv, d, **kw)
         return out
 
     (got,) = run(fn, slack)

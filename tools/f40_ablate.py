@@ -1,6 +1,7 @@
 """What bounds flash40 (the roofline kernel): timing-only ABLATIONS of its loop (DIAGNOSTIC builds,
-wrong results, never the product library), spliced into a copy of csrc/attention.hip at build time
-and timed against the product library on the level-1 shape (32 images x 8 heads, S = 4096, d = 40,
+wrong results, never the product library), spliced into a copy of csrc/attention_flash40.hip at build time
+(the one object rebuilt; the rest of the library is linked as built) and timed against the product
+library on the level-1 shape (32 images x 8 heads, S = 4096, d = 40,
 bench.py's `synthetic` inputs), arms interleaved in one process:
 
   noexp   the V phase's 64 v_exp_f32 per wave-tile removed (P = bf16(s - mu) instead of exp2):
@@ -104,10 +105,8 @@ MPHASE_CALL = """    mphase(t);
 """
 
 
-def instrument(text: str, name: str) -> str:
-    i0 = text.index("// ============================================================ flash40")
-    i1 = text.index("// kernel (per call, test hook")
-    body = text[i0:i1]
+def instrument(body: str, name: str) -> str:
+    """attention_flash40.hip with variant `name` spliced in (every anchor occurs exactly once)."""
     if name == "noexp":
         anchor, old, new = EXP_F4
         j = body.index(anchor)
@@ -204,13 +203,14 @@ def instrument(text: str, name: str) -> str:
         top = "  for (int t = 0; t < T; ++t) {\n"
         assert body.count(top) == 1
         body = body.replace(top, "  unsigned long long tp_ = f4_stamp();\n" + top)
-        body = STAMP_DEFS + body
-    out = text[:i0] + body + text[i1:]
+        head = '#include "attention_common.h"\n\nnamespace {\n'
+        assert body.count(head) == 1
+        body = body.replace(head, head + STAMP_DEFS)
     if name in ("novphase", "nomphase"):  # their outputs are garbage / NaN: keep the exact fix-up pass out
-        flag = "    return out_f32 ? __builtin_isnan(((const float*)o)[f]) : ((o[f] & 0x7FFF) > 0x7F80);"
-        assert out.count(flag) == 1
-        out = out.replace(flag, "    return false;")
-    return out
+        fix = "  const int rc_exact = launch_flash32_exact(a, p);\n"
+        assert body.count(fix) == 1
+        body = body.replace(fix, "  const int rc_exact = VD_OK;\n")
+    return body
 
 
 LOOP_OLD = """    if (t > 0) decide(t);
@@ -357,11 +357,12 @@ def build():
     for name in VARIANTS:
         src_dir = OUT / f"src_f40_{name}"
         src_dir.mkdir(exist_ok=True)
-        (src_dir / "attention.hip").write_text(instrument((B.CSRC / "attention.hip").read_text(), name))
+        (src_dir / "attention_flash40.hip").write_text(instrument((B.CSRC / "attention_flash40.hip").read_text(), name))
         defs = ['-DVD_BUILD_HASH="diag"', f'-DVD_BUILD_ARCH="{B.ARCH}"', f"-I{B.CSRC}", f"-I{ROOT / 'include'}"]
-        obj = OUT / f"attention_{name}.o"
-        subprocess.run([B.HIPCC, *B.CFLAGS, *defs, "-c", str(src_dir / "attention.hip"), "-o", str(obj)], check=True)
-        objs = [str(obj)] + [str(p) for p in sorted(B.BUILD.glob("*.o")) if p.stem != "attention"]
+        obj = OUT / f"attention_flash40_{name}.o"
+        subprocess.run([B.HIPCC, *B.CFLAGS, *defs, "-c", str(src_dir / "attention_flash40.hip"), "-o", str(obj)],
+                       check=True)
+        objs = [str(obj)] + [str(p) for p in sorted(B.BUILD.glob("*.o")) if p.stem != "attention_flash40"]
         lib = OUT / f"libvdiff_f40_{name}.so"
         subprocess.run([B.HIPCC, f"--offload-arch={B.ARCH}", "-shared", "-fPIC", "-o", str(lib), *objs,
                         "-L/opt/rocm/lib", "-lrccl"], check=True)

@@ -1,6 +1,7 @@
 """What bounds flash80 (the level-2 d = 80 self-attention): timing-only ABLATIONS of its loop
 (DIAGNOSTIC builds, wrong results, never the product library), spliced into a copy of
-csrc/attention.hip and timed against the product library on the level-2 shape (32 images x 8 heads,
+csrc/attention_flash80.hip (the one object rebuilt; the rest of the library is linked as built) and
+timed against the product library on the level-2 shape (32 images x 8 heads,
 S = 1024, d = 80, unit scale), arms interleaved in one process (tools/f40_ablate.py's method).
 
   nodma     no LDS-DMA issued or waited in the loop (the ring keeps tile 0-2's bytes)
@@ -38,10 +39,8 @@ LOOP = """    vphase(t);
 """
 
 
-def instrument(text: str, name: str) -> str:
-    i0 = text.index("// ============================================================ flash80")
-    i1 = text.index("// kernel (per call, test hook")
-    body = text[i0:i1]
+def instrument(body: str, name: str) -> str:
+    """attention_flash80.hip with variant `name` spliced in (every anchor occurs exactly once)."""
     if name == "nodma":
         for old in ("    if (g0) issue(t + 3);\n", "    if (!g0) issue(t + 3);\n"):
             assert body.count(old) == 1
@@ -62,7 +61,7 @@ def instrument(text: str, name: str) -> str:
     elif name == "nomphase":
         assert body.count("    mphase(t);\n") == 1
         body = body.replace("    mphase(t);\n", "")
-    return text[:i0] + body + text[i1:]
+    return body
 
 
 def build():
@@ -72,11 +71,12 @@ def build():
     for name in VARIANTS:
         src_dir = OUT / f"src_{name}"
         src_dir.mkdir(exist_ok=True)
-        (src_dir / "attention.hip").write_text(instrument((B.CSRC / "attention.hip").read_text(), name))
+        (src_dir / "attention_flash80.hip").write_text(instrument((B.CSRC / "attention_flash80.hip").read_text(), name))
         defs = ['-DVD_BUILD_HASH="diag"', f'-DVD_BUILD_ARCH="{B.ARCH}"', f"-I{B.CSRC}", f"-I{ROOT / 'include'}"]
-        obj = OUT / f"attention_{name}.o"
-        subprocess.run([B.HIPCC, *B.CFLAGS, *defs, "-c", str(src_dir / "attention.hip"), "-o", str(obj)], check=True)
-        objs = [str(obj)] + [str(p) for p in sorted(B.BUILD.glob("*.o")) if p.stem != "attention"]
+        obj = OUT / f"attention_flash80_{name}.o"
+        subprocess.run([B.HIPCC, *B.CFLAGS, *defs, "-c", str(src_dir / "attention_flash80.hip"), "-o", str(obj)],
+                       check=True)
+        objs = [str(obj)] + [str(p) for p in sorted(B.BUILD.glob("*.o")) if p.stem != "attention_flash80"]
         lib = OUT / f"libvdiff_f80_{name}.so"
         subprocess.run([B.HIPCC, f"--offload-arch={B.ARCH}", "-shared", "-fPIC", "-o", str(lib), *objs,
                         "-L/opt/rocm/lib", "-lrccl"], check=True)

@@ -27,11 +27,9 @@
 // Work per frame: 4 * S^2 * 512 FLOP (34.4 GFLOP at S = 4096); bytes: Q, K, V read and O
 // written once per frame from HBM (K/V re-read from L2 by the frame's 32 workgroups, which
 // the XCD-aware block order keeps on one XCD).
-#include "common.h"
+#include "attention_common.h"
 
 namespace {
-
-typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 constexpr int A5_D = 512, A5_NT = 256, A5_QW = 32, A5_QWG = 4 * A5_QW, A5_KT = 32;
 constexpr int A5_ROW = A5_D * 2;            // bytes per K / V row
@@ -334,26 +332,65 @@ __global__ __launch_bounds__(A5_NT, 1) void flash512_kernel(const bf16_t* __rest
     }
 }
 
+// Row softmax for the materialised-score attention of the VAE mid block (one head,
+// d = 512: S = 4096 keys per frame fits HBM easily, the flash kernels stop at d = 160).
+// Scores arrive fp32 in log2 units (the caller folded d^-1/2 * log2(e) into q):
+// p = exp2(s - max) / sum, written bf16 as the A operand of the P.V GEMM.  One
+// workgroup per row, 4 columns per thread-step, three passes over the row (max,
+// sum, write) — the row (16 KiB at 4096 keys) stays in L1/L2 between them.
+__global__ __launch_bounds__(NT) void softmax_rows_kernel(const float* __restrict__ s, int64_t lds,
+                                                          int64_t cols, bf16_t* __restrict__ p,
+                                                          int64_t ldp) {
+  __shared__ float red[NT / 64];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const float* row = s + (int64_t)blockIdx.x * lds;
+  bf16_t* out = p + (int64_t)blockIdx.x * ldp;
+  float m = -INFINITY;
+  for (int64_t c = 4 * tid; c < cols; c += 4 * NT) {
+    const float4 v = *(const float4*)(row + c);
+    m = fmaxf(m, fmaxf(fmaxf(v.x, v.y), fmaxf(v.z, v.w)));
+  }
+  m = wave_max(m);
+  if (lane == 0) red[w] = m;
+  __syncthreads();
+  m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+  __syncthreads();
+  float sum = 0.f;
+  for (int64_t c = 4 * tid; c < cols; c += 4 * NT) {
+    const float4 v = *(const float4*)(row + c);
+    sum += (exp2f(v.x - m) + exp2f(v.y - m)) + (exp2f(v.z - m) + exp2f(v.w - m));
+  }
+  sum = wave_sum(sum);
+  if (lane == 0) red[w] = sum;
+  __syncthreads();
+  const float inv = 1.f / ((red[0] + red[1]) + (red[2] + red[3]));
+  for (int64_t c = 4 * tid; c < cols; c += 4 * NT) {
+    const float4 v = *(const float4*)(row + c);
+    *(uint2*)(out + c) = make_uint2(pack2(exp2f(v.x - m) * inv, exp2f(v.y - m) * inv),
+                                    pack2(exp2f(v.z - m) * inv, exp2f(v.w - m) * inv));
+  }
+}
+
 }  // namespace
 
-// d = 512 (the VAE mid-block attention) for attention_entry (attention.hip).
-int launch_flash512(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, void* o,
-                    int64_t ldo, int64_t batch, int heads, int64_t sq, int64_t skv, int64_t kv_div, float scale,
-                    hipStream_t s, int out_f32) {
-  // 16-byte rows for the DMA pieces and the epilogue's 16-byte stores
-  if (((uintptr_t)o & 15) != 0 || ldo % (out_f32 ? 4 : 8) != 0) return VD_EINVAL;
-  if ((uint64_t)(skv - 1) * (uint64_t)ldk * 2 + A5_ROW >= 0x80000000ull ||
-      (uint64_t)(skv - 1) * (uint64_t)ldv * 2 + A5_ROW >= 0x80000000ull)
+// d = 512 (the VAE mid-block attention).  The plan (attention.hip) has checked o's 16-byte rows
+// (the epilogue's 16-byte stores) and sized the grid of A5_QWG-query blocks; the DMA pieces'
+// 31-bit byte range depends on the K/V strides, which the plan does not see.
+int vdattn::launch_flash512(const Args& a, const Plan& p) {
+  static_assert(A5_QWG == 128, "plan(): d = 512 grid");
+  if ((uint64_t)(a.skv - 1) * (uint64_t)a.ldk * 2 + A5_ROW >= 0x80000000ull ||
+      (uint64_t)(a.skv - 1) * (uint64_t)a.ldv * 2 + A5_ROW >= 0x80000000ull)
     return VD_EINVAL;
-  const int64_t nblk = (sq + A5_QWG - 1) / A5_QWG * heads * batch;
-  if (nblk > 0x7fffffff) return VD_EINVAL;
-  const float c = scale * 1.4426950408889634f;
-  const dim3 grid((unsigned)nblk);
-#define A5_LAUNCH(R)                                                                                          \
-  hipLaunchKernelGGL((flash512_kernel<R, 3>), grid, dim3(A5_NT), 0, s, (const bf16_t*)q, ldq, (const bf16_t*)k,  \
-                     ldk, (const bf16_t*)v, ldv, (bf16_t*)o, ldo, heads, sq, skv, kv_div, c, out_f32)
-  if (skv % A5_KT != 0) A5_LAUNCH(true);
-  else A5_LAUNCH(false);
-#undef A5_LAUNCH
+  const dim3 grid((unsigned)p.grid);
+  if (a.skv % A5_KT != 0) return launch(flash512_kernel<true, 3>, grid, A5_NT, a);
+  return launch(flash512_kernel<false, 3>, grid, A5_NT, a);
+}
+
+extern "C" int vd_softmax_rows(const float* s, int64_t ld_s, int64_t rows, int64_t cols, void* p, int64_t ld_p,
+                               vd_stream_t stream) {
+  VD_CHECK_ARG(s && p && rows > 0 && cols > 0 && cols % 4 == 0 && ld_s % 4 == 0 && ld_p % 4 == 0);
+  VD_CHECK_ARG(ld_s >= cols && ld_p >= cols && al16(s) && ((uintptr_t)p & 7) == 0 && rows < 0x7fffffff);
+  hipLaunchKernelGGL(softmax_rows_kernel, dim3((unsigned)rows), dim3(NT), 0, (hipStream_t)stream, s, ld_s, cols,
+                     (bf16_t*)p, ld_p);
   return vd_launch_status();
 }

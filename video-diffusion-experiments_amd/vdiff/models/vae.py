@@ -22,7 +22,7 @@ bf16 rows over (frame, y, x), and each op is a vdiff kernel:
     (softmax scale * log2 e folded into q's weight and bias), then ONE flash pass over every
     frame (vd_attention with d = 512 -> flash512_kernel, csrc/attention_d512.hip: no score
     matrix in memory; round 2 materialised a 64 MB fp32 S per frame and ran GEMM ->
-    vd_softmax_rows -> GEMM), out = O.W_o^T + b_o + x;
+    vd_softmax_rows -> GEMM; that row softmax is kept in the same file), out = O.W_o^T + b_o + x;
   * the encoder's Downsample2D(padding=0) — F.pad(x, (0, 1, 0, 1)) then a stride-2 conv
     without padding — is the conv loaders' pad-end mode (VD_CONV_PAD_END): no padded copy.
 Encoding runs in the same chunks: 8 frames' 512x512x128 activation is 0.5 GiB.

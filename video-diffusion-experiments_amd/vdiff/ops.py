@@ -6,6 +6,7 @@ non-CUDA tensors are rejected and a missing library raises.
 """
 from __future__ import annotations
 
+import collections
 import contextlib
 import ctypes as C
 import math
@@ -550,6 +551,32 @@ def attention(q, k, v, batch, heads, sq, skv, d, kv_div=1, scale=None, out=None,
                                 ATTN_KERNELS[kernel] | (ATTN_CAUSAL if causal else 0) | (tail << ATTN_TAIL_SHIFT),
                                 _stream()), "vd_attention_ex")
     return out
+
+
+ATTN_FAMILIES = {1: "flash", 2: "flash32", 3: "flash40", 4: "flash80", 5: "flash512"}  # VD_ATTN_K_*
+AttentionPlan = collections.namedtuple("AttentionPlan", "rc family qblk unit_scale grid exact_grid")
+
+
+def _attention_plan_query(o, ldo, batch, heads, sq, skv, d, kv_div, scale, out_f32, word):
+    """vd_attention_plan on raw values (o is an address): rc is its return code, not checked."""
+    fam, qb, us = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    g, eg = C.c_int64(0), C.c_int64(0)
+    rc = lib().vd_attention_plan(o, ldo, batch, heads, sq, skv, d, kv_div, scale, int(out_f32), word, C.byref(fam),
+                                 C.byref(qb), C.byref(us), C.byref(g), C.byref(eg))
+    return AttentionPlan(rc, fam.value, qb.value, us.value, g.value, eg.value)
+
+
+def attention_plan(q, k, v, batch, heads, sq, skv, d, kv_div=1, scale=None, out=None, out_f32=False, kernel="auto",
+                   causal=False, tail=0):
+    """What attention() would run for the same arguments (vd_attention_plan: no launch, works
+    without a device): an AttentionPlan whose family is a name of ATTN_FAMILIES.  q / k / v are
+    not looked at; out=None stands for the aligned, dense output attention() would allocate."""
+    o, ldo = (256, heads * d) if out is None else (_p(out), out.stride(0))
+    scale = d ** -0.5 if scale is None else scale
+    p = _attention_plan_query(o, ldo, batch, heads, sq, skv, d, kv_div, scale, out_f32,
+                              ATTN_KERNELS[kernel] | (ATTN_CAUSAL if causal else 0) | (tail << ATTN_TAIL_SHIFT))
+    check(p.rc, "vd_attention_plan")
+    return p._replace(family=ATTN_FAMILIES[p.family])
 
 
 def temporal_attention(q, k, v, batch, frames, positions, heads, d, scale=None, out=None, rope_theta=None,
