@@ -548,9 +548,42 @@ int vd_block_transpose(const void* src, void* dst, int64_t nb, int64_t na, int64
  *   op 3, VD_ROWS_SCALE: out[r][c] = bf16(x[r][c] * *y) over C columns; out == x is allowed
  *   (FreeU's hidden_states[:, :C/2] *= b, on the column slice alone).  y_div and y_period are
  *   not read.
+ *   Ops 4 and 5 are FreeNoise (diffusers' FreeNoiseTransformerBlock: a motion transformer block
+ *   runs on sliding windows of L frames and the window outputs are averaged with per-frame
+ *   weights).  They ride on this entry point for the same reason as ops 2 and 3.  The rows are
+ *   (video b, frame f, position p); op = VD_ROWS_WIN_GATHER or VD_ROWS_WIN_MERGE, OR-ed with
+ *   VD_ROWS_WIN_STRIDE(s) (the low byte is the op, as VD_ATTN_TAIL(n) rides on its kernel word);
+ *   F = y_period frames, hw = y_div positions per frame, L = ldy the context length, rows =
+ *   B * F * hw the UN-windowed row count.  Windows, with integer division: nReg = (F - L) / s + 1
+ *   regular windows start at frame w * s; when (nReg - 1) * s + L < F one more tail window starts
+ *   at F - L and owns the last tail_len = F - ((nReg - 1) * s + L) frames; nW = nReg (+ 1).
+ *   op 4, VD_ROWS_WIN_GATHER: out[((b * nW + w) * L + j) * hw + p] = x[(b * F + start_w + j) * hw + p],
+ *   a 16-byte copy: the rows of B * nW videos of L frames, which the temporal kernels take as
+ *   they are.  x holds rows rows, out B * nW * L * hw.  y == NULL and y_f32 == 0.
+ *   op 5, VD_ROWS_WIN_MERGE, the inverse: x holds the B * nW * L * hw window rows, out rows rows.
+ *   A frame f that regular windows cover becomes
+ *     out = bf16( (sum_w wt[f - w s] * x_w[f - w s]) / (sum_w wt[f - w s]) ),
+ *   both sums in fp32 over the regular windows that hold f in ascending w (fmaf per term, one
+ *   correctly rounded division, one rounding to bf16; no atomics), so the order depends on
+ *   (F, L, s) alone, never on B, hw or C.  The last tail_len frames, which no regular window
+ *   reaches, take the tail window's value as it is; the tail window's other frames are not read.
+ *   y = L fp32 weights in DEVICE memory (y_f32 == 1, 4-byte aligned), read inside the launch
+ *   only, so the call stays graph-capturable.  They must be finite and positive: that is the
+ *   caller's duty, the entry point cannot refuse a device value.
+ *   VD_EINVAL for both: s < 1 or s > L, L < 1 or L > 32, F < L, rows not a multiple of F * hw,
+ *   x NULL, out == x (so a plain op 4 or 5, which carries s = 0, is refused), any bit above the
+ *   low byte on ops 0-3; op 5 with y NULL, misaligned or y_f32 != 1; op 4 with y or y_f32 set.
  * vd_upsample_nearest2x: rows of n_img h x w images -> rows of their nearest x2 upsample
  *   (Upsample2D's F.interpolate(scale_factor=2.0, mode="nearest")). */
-enum { VD_ROWS_ADD = 0, VD_ROWS_SILU = 1, VD_ROWS_FREEU_FILTER = 2, VD_ROWS_SCALE = 3 };
+enum {
+  VD_ROWS_ADD = 0,
+  VD_ROWS_SILU = 1,
+  VD_ROWS_FREEU_FILTER = 2,
+  VD_ROWS_SCALE = 3,
+  VD_ROWS_WIN_GATHER = 4,
+  VD_ROWS_WIN_MERGE = 5
+};
+#define VD_ROWS_WIN_STRIDE(s) ((s) << 8)
 int vd_rows_eltwise(int32_t op, const void* x, int64_t ldx, const void* y, int64_t ldy, int32_t y_f32,
                     int64_t y_div, int64_t y_period, int64_t rows, int64_t C, void* out, int64_t ldo,
                     vd_stream_t stream);

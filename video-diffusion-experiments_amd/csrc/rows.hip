@@ -27,6 +27,7 @@ __device__ __forceinline__ void load8_any(const void* p, int is_f32, float* f) {
 // op 0: out[r] = (x ? x[r] : 0) + y[(r / y_div) % y_period]     (y bf16 or fp32)
 // op 1: out[r] = silu(x[r])
 // op 3: out[r] = x[r] * *y                                        (y one fp32 on the device)
+// (op 2 is freeu_filter_kernel, ops 4 and 5 win_gather_kernel / win_merge_kernel below)
 __global__ void rows_eltwise_kernel(int op, const bf16_t* x, int64_t ldx, const void* y, int64_t ldy, int y_f32,
                                     int64_t y_div, int64_t y_period, int64_t rows, int64_t C, bf16_t* out,
                                     int64_t ldo) {
@@ -212,6 +213,94 @@ __global__ __launch_bounds__(NT) void freeu_filter_kernel(const bf16_t* x, int64
   }
 }
 
+// Ops 4 and 5, FreeNoise's sliding windows over the frames of (video b, frame f, position p) rows
+// (diffusers' FreeNoiseTransformerBlock; include/vdiff.h has the geometry).  Window w < nReg
+// starts at frame w * s, the tail window (index nReg, when there is one) at F - L.
+// One workgroup works inside one frame: the window list and the normaliser are wave-uniform
+// (scalar registers), and a thread walks the frame's hw * C / 8 16-byte chunks with a
+// (row, chunk) pair advanced by the host's (dr, dc) = divmod(gridDim.y * NT, C / 8): one 32-bit
+// division per thread, none per element.
+struct WinGeo {
+  int F, L, s, nReg, nW;  // frames, context length, stride, regular windows, all windows
+  int hw, cpr;            // positions per frame, 16-byte chunks per row
+  int dr, dc;             // divmod(gridDim.y * NT, cpr)
+};
+
+struct WinPos {
+  int r, c;
+  __device__ __forceinline__ WinPos(const WinGeo& g) {
+    const unsigned i = blockIdx.y * NT + threadIdx.x;
+    r = (int)(i / (unsigned)g.cpr);
+    c = (int)(i - (unsigned)r * (unsigned)g.cpr);
+  }
+  __device__ __forceinline__ void next(const WinGeo& g) {
+    r += g.dr;
+    c += g.dc;
+    if (c >= g.cpr) {
+      c -= g.cpr;
+      ++r;
+    }
+  }
+};
+
+// op 4: out frame (b, w, j) <- x frame (b, start_w + j); blockIdx.x = (b * nW + w) * L + j
+__global__ __launch_bounds__(NT) void win_gather_kernel(const bf16_t* x, int64_t ldx, WinGeo g, bf16_t* out,
+                                                        int64_t ldo) {
+  const int fo = blockIdx.x, j = fo % g.L, bw = fo / g.L, w = bw % g.nW, b = bw / g.nW;
+  const int start = w < g.nReg ? w * g.s : g.F - g.L;
+  const bf16_t* src = x + ((int64_t)b * g.F + start + j) * g.hw * ldx;
+  bf16_t* dst = out + (int64_t)fo * g.hw * ldo;
+  for (WinPos p(g); p.r < g.hw; p.next(g))
+    *(uint4*)(dst + (int64_t)p.r * ldo + p.c * 8) = *(const uint4*)(src + (int64_t)p.r * ldx + p.c * 8);
+}
+
+// op 5: out frame (b, f) <- the weighted mean of the regular windows that hold f, ascending w, or
+// the tail window's frame where no regular window reaches; blockIdx.x = b * F + f.  Four
+// windows' loads are in flight before the first is consumed (the default L = 16, s = 4 has at
+// most four per frame); the order of the fp32 sum is that of w whatever the grouping.
+constexpr int WIN_G = 4;
+__global__ __launch_bounds__(NT) void win_merge_kernel(const bf16_t* x, int64_t ldx, const float* wt, WinGeo g,
+                                                       bf16_t* out, int64_t ldo) {
+  const int b = blockIdx.x / g.F, f = blockIdx.x - b * g.F;
+  bf16_t* dst = out + (int64_t)blockIdx.x * g.hw * ldo;
+  const int64_t vid = (int64_t)b * g.nW;  // the video's first window
+  if (f >= (g.nReg - 1) * g.s + g.L) {    // a tail frame: the tail window's value as it is
+    const bf16_t* src = x + ((vid + g.nReg) * g.L + (f - (g.F - g.L))) * g.hw * ldx;
+    for (WinPos p(g); p.r < g.hw; p.next(g))
+      *(uint4*)(dst + (int64_t)p.r * ldo + p.c * 8) = *(const uint4*)(src + (int64_t)p.r * ldx + p.c * 8);
+    return;
+  }
+  const int w_lo = f < g.L ? 0 : (f - g.L) / g.s + 1;
+  const int w_hi = min(f / g.s, g.nReg - 1);
+  float den = 0.f;
+  for (int w = w_lo; w <= w_hi; ++w) den += wt[f - w * g.s];
+  for (WinPos p(g); p.r < g.hw; p.next(g)) {
+    float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (int w0 = w_lo; w0 <= w_hi; w0 += WIN_G) {
+      uint4 v[WIN_G];
+#pragma unroll
+      for (int k = 0; k < WIN_G; ++k) {
+        const int w = w0 + k, j = f - w * g.s;
+        if (w <= w_hi) v[k] = *(const uint4*)(x + (((vid + w) * g.L + j) * g.hw + p.r) * ldx + p.c * 8);
+      }
+#pragma unroll
+      for (int k = 0; k < WIN_G; ++k) {
+        const int w = w0 + k;
+        if (w <= w_hi) {
+          const float a = wt[f - w * g.s];
+          float e[8];
+          unpack8(v[k], e);
+#pragma unroll
+          for (int q = 0; q < 8; ++q) acc[q] = fmaf(a, e[q], acc[q]);
+        }
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < 8; ++q) acc[q] = acc[q] / den;
+    *(uint4*)(dst + (int64_t)p.r * ldo + p.c * 8) = pack8(acc);
+  }
+}
+
 unsigned grid_for(int64_t total) {
   const int64_t b = (total + NT - 1) / NT;
   return (unsigned)(b < 16384 ? (b > 0 ? b : 1) : 16384);
@@ -224,10 +313,36 @@ inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 extern "C" int vd_rows_eltwise(int32_t op, const void* x, int64_t ldx, const void* y, int64_t ldy, int32_t y_f32,
                                int64_t y_div, int64_t y_period, int64_t rows, int64_t C, void* out, int64_t ldo,
                                vd_stream_t stream) {
-  VD_CHECK_ARG(op >= VD_ROWS_ADD && op <= VD_ROWS_SCALE && out && rows > 0 && C > 0 && C % 8 == 0 && ldo % 8 == 0 &&
-               ldo >= C);
+  // ops 4 and 5 carry the window stride above the low byte (VD_ROWS_WIN_STRIDE); no other op does
+  const int32_t win_s = op >> 8;
+  const bool win = op >= 0 && ((op & 0xff) == VD_ROWS_WIN_GATHER || (op & 0xff) == VD_ROWS_WIN_MERGE);
+  if (win) op &= 0xff;
+  VD_CHECK_ARG(op >= VD_ROWS_ADD && op <= VD_ROWS_WIN_MERGE && out && rows > 0 && C > 0 && C % 8 == 0 &&
+               ldo % 8 == 0 && ldo >= C);
   VD_CHECK_ARG(al16(out));
   if (x) VD_CHECK_ARG(al16(x) && ldx % 8 == 0 && ldx >= C);
+  if (win) {
+    const int64_t F = y_period, hw = y_div, L = ldy, s = win_s;
+    VD_CHECK_ARG(x && out != x && L >= 1 && L <= 32 && s >= 1 && s <= L && F >= L && F <= (1 << 20) && hw >= 1);
+    VD_CHECK_ARG(hw * (C / 8) <= 0x3fffffff && rows % (F * hw) == 0);
+    if (op == VD_ROWS_WIN_MERGE)  // the L weights: fp32 on the device
+      VD_CHECK_ARG(y && ((uintptr_t)y & 3) == 0 && y_f32 == 1);
+    else
+      VD_CHECK_ARG(y == nullptr && y_f32 == 0);
+    const int64_t B = rows / (F * hw), nReg = (F - L) / s + 1, nW = nReg + ((nReg - 1) * s + L < F ? 1 : 0);
+    const int64_t gx = op == VD_ROWS_WIN_GATHER ? B * nW * L : B * F;
+    VD_CHECK_ARG(gx <= 0x7fffffff);
+    const int64_t cpr = C / 8, by = (hw * cpr + NT - 1) / NT, gy = by < 4096 ? by : 4096;
+    const WinGeo g{(int)F, (int)L, (int)s, (int)nReg, (int)nW, (int)hw, (int)cpr, (int)(gy * NT / cpr),
+                   (int)(gy * NT % cpr)};
+    if (op == VD_ROWS_WIN_GATHER)
+      hipLaunchKernelGGL(win_gather_kernel, dim3((unsigned)gx, (unsigned)gy), dim3(NT), 0, (hipStream_t)stream,
+                         (const bf16_t*)x, ldx, g, (bf16_t*)out, ldo);
+    else
+      hipLaunchKernelGGL(win_merge_kernel, dim3((unsigned)gx, (unsigned)gy), dim3(NT), 0, (hipStream_t)stream,
+                         (const bf16_t*)x, ldx, (const float*)y, g, (bf16_t*)out, ldo);
+    return vd_launch_status();
+  }
   if (op == 0) {
     VD_CHECK_ARG(y && al16(y) && ldy >= C && ldy % (y_f32 ? 4 : 8) == 0 && y_div > 0 && y_period > 0);
   } else {

@@ -415,6 +415,44 @@ class Transformer2DModel(nn.Module):
         return Transformer2DModelOutput(out) if return_dict else (out,)
 
 
+FREE_NOISE_WEIGHTING_SCHEMES = ("flat", "pyramid", "delayed_reverse_sawtooth")
+
+
+def free_noise_frame_weights(num_frames, weighting_scheme="pyramid"):
+    """diffusers' FreeNoiseTransformerBlock._get_frame_weights: the weight of each frame of a
+    window.  pyramid 4 -> [1, 2, 2, 1], 5 -> [1, 2, 3, 2, 1]; delayed_reverse_sawtooth 4 ->
+    [0.01, 2, 2, 1], 5 -> [0.01, 0.01, 3, 2, 1]."""
+    n = int(num_frames)
+    if weighting_scheme == "flat":
+        return [1.0] * n
+    mid = (n + 1) // 2
+    down = list(range(mid, 0, -1))
+    if weighting_scheme == "pyramid":
+        up = list(range(1, mid + 1))
+        return [float(v) for v in (up + down if n % 2 == 0 else up[:-1] + down)]
+    if weighting_scheme == "delayed_reverse_sawtooth":
+        return [float(v) for v in ([0.01] * (mid - 1) + [mid] + down if n % 2 == 0 else [0.01] * (mid - 1) + down)]
+    raise ValueError(f"weighting_scheme {weighting_scheme!r}: one of {FREE_NOISE_WEIGHTING_SCHEMES}")
+
+
+def frame_rows_to_tokens(rows, n_vid, frames, hw):
+    """rows (video, frame, position) -> token rows (video, position, frame), per video."""
+    tok = torch.empty_like(rows)
+    for i in range(n_vid):
+        ops.block_transpose(rows[i * frames * hw:(i + 1) * frames * hw], frames, hw, 1,
+                            out=tok[i * frames * hw:(i + 1) * frames * hw])
+    return tok
+
+
+def tokens_to_frame_rows(tok, n_vid, frames, hw):
+    """token rows (video, position, frame) -> rows (video, frame, position), per video."""
+    rows = torch.empty_like(tok)
+    for i in range(n_vid):
+        ops.block_transpose(tok[i * frames * hw:(i + 1) * frames * hw], hw, frames, 1,
+                            out=rows[i * frames * hw:(i + 1) * frames * hw])
+    return rows
+
+
 class AnimateDiffTransformer3D(nn.Module):
     """diffusers:AnimateDiffTransformer3D (motion module).  GroupNorm statistics
     span all F frames of a video; attention runs over frames per position."""
@@ -429,11 +467,66 @@ class AnimateDiffTransformer3D(nn.Module):
             inner, heads, dim_head, double_self_attention=True, positional_embeddings="sinusoidal",
             num_positional_embeddings=max_seq_length)])
         self.proj_out = Linear(inner, in_channels)
+        # FreeNoise (diffusers' FreeNoiseTransformerBlock, set by UNetMotionModel.enable_free_noise):
+        # the transformer block runs on sliding windows of context_length frames and the window
+        # outputs are averaged with the weighting scheme's per-frame weights
+        self.max_seq_length = max_seq_length
+        self.context_length = self.context_stride = self.weighting_scheme = None
+        self._fn_wt = None  # fp32 [context_length] on the device while enabled (the merge reads it there)
+
+    @property
+    def free_noise_enabled(self) -> bool:
+        return self.context_length is not None
+
+    def prepare(self):
+        """(Re-)make the device operand of FreeNoise: the window's frame weights."""
+        self._fn_wt = None
+        dev = next(self.parameters()).device
+        if self.free_noise_enabled and dev.type == "cuda":
+            self._fn_wt = torch.tensor(free_noise_frame_weights(self.context_length, self.weighting_scheme),
+                                       dtype=torch.float32, device=dev)
+
+    def _free_noise_windows(self, frames, dist=None):
+        """(L, s, device weights) when this call runs windowed, None for the un-windowed path
+        (FreeNoise off, or one window: frames == context_length)."""
+        if not self.free_noise_enabled:
+            total = frames * getattr(dist, "world", 1)
+            if total > self.max_seq_length:  # refused here, before a launch indexes the PE table past its end
+                raise ValueError(f"{total} frames exceed motion_max_seq_length={self.max_seq_length} (the positional "
+                                 "table and the temporal attention end there): enable_free_noise() runs longer videos")
+            return None
+        if dist is not None:
+            raise NotImplementedError("FreeNoise under frame sharding (FrameShard) is not supported: a window's "
+                                      "frames would span ranks; detach the FrameShard or disable_free_noise()")
+        L = self.context_length
+        if frames < L:
+            raise ValueError(f"FreeNoise: {frames} frames are fewer than context_length={L}")
+        if frames == L:
+            return None
+        if self._fn_wt is None:
+            self.prepare()
+        return L, self.context_stride, self._fn_wt
 
     def run(self, x: Act, ctx: Ctx) -> Act:
         hw = x.h * x.w
         B, Fl = ctx.batch, ctx.frames
         dist = ctx.dist
+        fn = self._free_noise_windows(Fl, dist)
+        if fn is not None:
+            # the motion norm over all frames, proj_in as a plain GEMM (its norm1 + PE epilogue
+            # indexes the PE by absolute frame), then the block on the windows as B * nW videos
+            # of L frames — the PE by frame in window, temporal_fold deciding for that shape —
+            # and the weighted merge back to (b, f, p) rows before proj_out
+            L, s, wt = fn
+            blk = self.transformer_blocks[0]
+            hn = ops.group_norm(x.t, B, Fl * hw, self.groups, 1e-6, self.norm._g, self.norm._b, two_pass=False,
+                                n_split=Fl * ops.gn_splits_per_frame(hw))
+            h = ops.gemm(hn, self.proj_in._w, bias=self.proj_in._b)
+            win = ops.window_gather(h, B, Fl, hw, L, s)
+            win = blk.run_temporal(win, win.shape[0] // (L * hw), L, hw, n=None)
+            h = ops.window_merge(win, wt, B, Fl, hw, L, s)
+            out = ops.gemm(h, self.proj_out._w, bias=self.proj_out._b, res=x.t)
+            return Act(out, x.n, x.h, x.w)
         # the motion norm's records (C <= 2560: per-group) all-gathered rank-major, no transpose copy
         gather = dist.gather_gn_records if dist is not None else None
         blk = self.transformer_blocks[0]
@@ -489,18 +582,25 @@ class AnimateDiffTransformer3D(nn.Module):
         hw = hh * ww
         x5 = hidden_states.reshape(b, num_frames, c, hh, ww).permute(0, 2, 1, 3, 4)   # (B, C, F, H, W)
         hn = fmap_rows(self.norm(x5))                                                # rows (b, f, p)
-        tok = torch.empty_like(hn)
-        for i in range(b):  # permute(0,3,4,2,1): rows (b, f, p) -> tokens (b, p, f)
-            ops.block_transpose(hn[i * num_frames * hw:(i + 1) * num_frames * hw], num_frames, hw, 1,
-                                out=tok[i * num_frames * hw:(i + 1) * num_frames * hw])
-        h = self.proj_in(tok.view(b * hw, num_frames, c))
-        for blk in self.transformer_blocks:
-            h = blk(h, encoder_hidden_states=encoder_hidden_states, timestep=timestep)
-        h = token_rows(self.proj_out(h))
-        back = torch.empty_like(h)
-        for i in range(b):  # tokens (b, p, f) -> rows (b, f, p)
-            ops.block_transpose(h[i * num_frames * hw:(i + 1) * num_frames * hw], hw, num_frames, 1,
-                                out=back[i * num_frames * hw:(i + 1) * num_frames * hw])
+        fn = self._free_noise_windows(num_frames)
+        # permute(0,3,4,2,1): rows (b, f, p) -> tokens (b, p, f)
+        h = self.proj_in(frame_rows_to_tokens(hn, b, num_frames, hw).view(b * hw, num_frames, c))
+        if fn is None:
+            for blk in self.transformer_blocks:
+                h = blk(h, encoder_hidden_states=encoder_hidden_states, timestep=timestep)
+        else:
+            # FreeNoise: gather and merge where the rows are (b, f, p); the block sees every window
+            # as one more video, tokens (B * nW * H * W, L, C) — diffusers' FreeNoiseTransformerBlock
+            # loops over the windows inside one call on (B * H * W, F, C)
+            L, s, wt = fn
+            win = ops.window_gather(tokens_to_frame_rows(token_rows(h), b, num_frames, hw), b, num_frames, hw, L, s)
+            bw = win.shape[0] // (L * hw)
+            h = frame_rows_to_tokens(win, bw, L, hw).view(bw * hw, L, -1)
+            for blk in self.transformer_blocks:
+                h = blk(h, encoder_hidden_states=encoder_hidden_states, timestep=timestep)
+            h = ops.window_merge(tokens_to_frame_rows(token_rows(h), bw, L, hw), wt, b, num_frames, hw, L, s)
+            h = frame_rows_to_tokens(h, b, num_frames, hw).view(b * hw, num_frames, -1)
+        back = tokens_to_frame_rows(token_rows(self.proj_out(h)), b, num_frames, hw)
         return add(rows_fmap(back, (bf_, c, hh, ww)), hidden_states)
 
 

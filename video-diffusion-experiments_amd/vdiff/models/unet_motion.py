@@ -21,8 +21,9 @@ import torch.nn as nn
 
 from .. import ops
 from ..config import down_block_plan, get_config, up_block_plan
-from .blocks import (CrossAttnDownBlockMotion, CrossAttnUpBlockMotion, Ctx, DownBlockMotion,
-                     ResnetBlock2D, UNetMidBlockCrossAttnMotion, UpBlockMotion)
+from .blocks import (FREE_NOISE_WEIGHTING_SCHEMES, AnimateDiffTransformer3D, CrossAttnDownBlockMotion,
+                     CrossAttnUpBlockMotion, Ctx, DownBlockMotion, ResnetBlock2D, UNetMidBlockCrossAttnMotion,
+                     UpBlockMotion)
 from .layers import Act, Conv2d, GroupNorm, SiLU, TimestepEmbedding, Timesteps, bf, f32, fmap_rows, token_rows
 
 
@@ -179,6 +180,43 @@ class UNetMotionModel(nn.Module):
         for blk in self.up_blocks:
             blk.s1 = blk.s2 = blk.b1 = blk.b2 = None
             blk.prepare()
+
+    # ------------------------------------------------------------------ FreeNoise
+    def motion_modules_in_order(self):
+        return [m for m in self.modules() if isinstance(m, AnimateDiffTransformer3D)]
+
+    def enable_free_noise(self, context_length=16, context_stride=4, weighting_scheme="pyramid"):
+        """diffusers' AnimateDiffFreeNoiseMixin on the UNet: every motion module runs its
+        transformer block on sliding windows of context_length frames, context_stride apart, and
+        averages the window outputs with the scheme's per-frame weights (vd_rows_eltwise ops 4
+        and 5 around the unchanged temporal kernels), so a video may be longer than
+        motion_max_seq_length.  context_length None is motion_max_seq_length.  A call with
+        exactly context_length frames runs as without FreeNoise, one with fewer raises.  A
+        DenoiseLoop built afterwards captures the windowed launches, one built before keeps
+        running without them."""
+        mlen = self.config["motion_max_seq_length"]
+        L = mlen if context_length is None else context_length
+        if not isinstance(L, int) or not isinstance(context_stride, int) or isinstance(L, bool):
+            raise ValueError(f"context_length and context_stride must be integers, got {L!r}, {context_stride!r}")
+        if L < 1 or L > mlen:
+            raise ValueError(f"context_length {L} is outside 1..motion_max_seq_length={mlen}: the positional "
+                             "table and the temporal kernels end there")
+        if not 1 <= context_stride <= L:
+            raise ValueError(f"context_stride {context_stride} is outside 1..context_length={L}")
+        if weighting_scheme not in FREE_NOISE_WEIGHTING_SCHEMES:
+            raise ValueError(f"weighting_scheme {weighting_scheme!r}: one of {FREE_NOISE_WEIGHTING_SCHEMES}")
+        for m in self.motion_modules_in_order():
+            m.context_length, m.context_stride, m.weighting_scheme = L, context_stride, weighting_scheme
+            m.prepare()
+
+    def disable_free_noise(self):
+        for m in self.motion_modules_in_order():
+            m.context_length = m.context_stride = m.weighting_scheme = None
+            m.prepare()
+
+    @property
+    def free_noise_enabled(self) -> bool:
+        return any(m.free_noise_enabled for m in self.motion_modules_in_order())
 
     def forward_rows(self, x_rows, h, w, ctx: Ctx):
         """Packed NHWC input rows [batch*frames*h*w, 8] -> eps rows fp32 [..., out_channels]."""

@@ -846,6 +846,63 @@ def scale_rows_(x_slice, g_dev):
     return x_slice
 
 
+ROWS_WIN_GATHER, ROWS_WIN_MERGE = 4, 5  # VD_ROWS_WIN_GATHER, VD_ROWS_WIN_MERGE
+ROWS_WIN_STRIDE_SHIFT = 8               # VD_ROWS_WIN_STRIDE(s) = s << 8
+
+
+def window_starts(F, L, s):
+    """FreeNoise's windows over F frames: the start frame of every window of L frames — the
+    regular ones at w * s, then the tail window at F - L when they leave frames uncovered — and
+    tail_len, the number of last frames only the tail window holds (0 without one)."""
+    if not (1 <= s <= L <= F):
+        raise ValueError(f"windows need 1 <= stride <= context_length <= frames, got {s}, {L}, {F}")
+    starts = list(range(0, F - L + 1, s))
+    tail_len = F - (starts[-1] + L)
+    if tail_len:
+        starts.append(F - L)
+    return starts, tail_len
+
+
+def window_gather(x, B, F, hw, L, s, out=None):
+    """The rows (b, f, p) of B videos of F frames -> the rows (b * nW + w, j, p) of their
+    window_starts(F, L, s) windows of L frames (vd_rows_eltwise op 4, a copy).  x may have a row
+    stride above its width; `out` may be a column slice, never x itself."""
+    _dev(x, out)
+    if x.shape[0] != B * F * hw:
+        raise ValueError(f"window_gather: {x.shape[0]} rows are not {B} videos of {F} frames x {hw} positions")
+    nW = len(window_starts(F, L, s)[0])
+    if out is None:
+        out = torch.empty(B * nW * L * hw, x.shape[1], device=x.device, dtype=BF16)
+    if out.shape[0] != B * nW * L * hw:
+        raise ValueError(f"window_gather: out holds {out.shape[0]} rows, the {nW} windows need {B * nW * L * hw}")
+    check(lib().vd_rows_eltwise(ROWS_WIN_GATHER | (s << ROWS_WIN_STRIDE_SHIFT), _p(x), _rows(x), None, L, 0, hw, F,
+                                x.shape[0], x.shape[1], _p(out), _rows(out), _stream()),
+          "vd_rows_eltwise(window_gather)")
+    return out
+
+
+def window_merge(xw, wt_dev, B, F, hw, L, s, out=None):
+    """window_gather's inverse with weights (vd_rows_eltwise op 5): frame f becomes the mean of
+    the regular windows that hold it, weighted by wt_dev[frame in window] (L positive fp32 on the
+    device, read inside the launch), summed in fp32 in ascending window order; the frames only
+    the tail window holds take its value."""
+    _dev(xw, wt_dev, out)
+    if wt_dev.dtype != torch.float32 or wt_dev.dim() != 1 or wt_dev.numel() != L or not wt_dev.is_contiguous():
+        raise ValueError(f"window_merge wt_dev: expected {L} contiguous fp32 weights on the device, got "
+                         f"{wt_dev.dtype} x {tuple(wt_dev.shape)}")
+    nW = len(window_starts(F, L, s)[0])
+    if xw.shape[0] != B * nW * L * hw:
+        raise ValueError(f"window_merge: {xw.shape[0]} rows are not {B} x {nW} windows of {L} frames x {hw} positions")
+    if out is None:
+        out = torch.empty(B * F * hw, xw.shape[1], device=xw.device, dtype=BF16)
+    if out.shape[0] != B * F * hw:
+        raise ValueError(f"window_merge: out holds {out.shape[0]} rows, {B} videos of {F} frames need {B * F * hw}")
+    check(lib().vd_rows_eltwise(ROWS_WIN_MERGE | (s << ROWS_WIN_STRIDE_SHIFT), _p(xw), _rows(xw), _p(wt_dev), L, 1,
+                                hw, F, out.shape[0], xw.shape[1], _p(out), _rows(out), _stream()),
+          "vd_rows_eltwise(window_merge)")
+    return out
+
+
 def upsample2x_rows(x, n_img, h, w, out=None):
     _dev(x, out)
     if out is None:

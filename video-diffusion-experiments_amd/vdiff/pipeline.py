@@ -136,6 +136,8 @@ class DenoiseLoop:
         # the FreeU scalars the step's launches (and the graph) read: kept alive for this loop's
         # life, whatever enable_freeu / disable_freeu does to the blocks afterwards
         self.freeu_operands = [b._freeu for b in unet.up_blocks]
+        # likewise FreeNoise's window weights (enable_free_noise / disable_free_noise)
+        self.free_noise_operands = [m._fn_wt for m in unet.motion_modules_in_order()]
         # conv_in + down_blocks[0].resnets[0] once for both CFG halves (UNetMotionModel.forward_rows)
         self.cfg_dedup = True
         self.use_graph = use_graph
@@ -262,6 +264,7 @@ class AnimateDiffPipeline:
         self.image_encoder = None
         self.feature_extractor = None
         self.image_projection = None
+        self._free_noise = None  # (context_length, context_stride, noise_type) while FreeNoise is enabled
         # the dtype the initial noise is drawn in (diffusers: prompt_embeds.dtype, i.e. the
         # pipeline's torch_dtype, fp32 when none is given); from_config keeps the reference's fp16
         self.torch_dtype = None
@@ -331,6 +334,79 @@ class AnimateDiffPipeline:
 
     def disable_freeu(self):
         self.unet.disable_freeu()
+
+    # ------------------------------------------------------------------ FreeNoise
+    FREE_NOISE_NOISE_TYPES = ("shuffle_context", "repeat_context", "random")
+
+    def enable_free_noise(self, context_length=16, context_stride=4, weighting_scheme="pyramid",
+                          noise_type="shuffle_context", prompt_interpolation_callback=None):
+        """diffusers' AnimateDiffFreeNoiseMixin.enable_free_noise: the motion modules run on sliding
+        windows (UNetMotionModel.enable_free_noise) and the text-to-video pipeline reschedules its
+        initial noise (_prepare_latents_free_noise), so num_frames may exceed
+        motion_max_seq_length.  The next __call__ builds its DenoiseLoop, and so its graph, with it."""
+        if noise_type not in self.FREE_NOISE_NOISE_TYPES:
+            raise ValueError(f"noise_type {noise_type!r}: one of {self.FREE_NOISE_NOISE_TYPES}")
+        if prompt_interpolation_callback is not None:
+            raise NotImplementedError("prompt_interpolation_callback (FreeNoise prompt travel) is not supported: "
+                                      "per-frame text embeddings need per-frame cross-attention K/V")
+        self.unet.enable_free_noise(context_length, context_stride, weighting_scheme)
+        m = self.unet.motion_modules_in_order()[0]
+        self._free_noise = (m.context_length, m.context_stride, noise_type)
+
+    def disable_free_noise(self):
+        self._free_noise = None
+        self.unet.disable_free_noise()
+
+    @property
+    def free_noise_enabled(self) -> bool:
+        return getattr(self, "_free_noise", None) is not None
+
+    def enable_free_noise_split_inference(self, spatial_split_size=256, temporal_split_size=16):
+        raise NotImplementedError("enable_free_noise_split_inference (diffusers' SplitInferenceModule memory "
+                                  "splitting) is not supported: the windows run as one batch")
+
+    def _prepare_latents_free_noise(self, batch, num_frames, h, w, generator=None, latents=None, device=None):
+        """diffusers' AnimateDiffFreeNoiseMixin._prepare_latents_free_noise, in pure torch (runs on
+        the CPU with a CPU generator): noise over num_frames frames in which distant windows see
+        correlated noise, before init_noise_sigma.
+          shuffle_context  all num_frames frames are drawn; then for i in range(L, F, s) frames
+                           i .. i + s take frames i - L .. i - L + s in a randperm order drawn from
+                           the same generator on its device (a prefix when they do not fit);
+          repeat_context   L frames are drawn and tiled;
+          random           as drawn.
+        `latents` with num_frames frames pass through unchanged; with L frames they are tiled to
+        num_frames and, under shuffle_context, shuffled as above; any other length is refused."""
+        L, s, noise_type = self._free_noise
+        device = torch.device(device if device is not None else self.unet.device)
+        dtype = self.torch_dtype or torch.float32
+        C = self.unet.config["in_channels"]
+        if latents is None:
+            draw = L if noise_type == "repeat_context" else num_frames
+            latents = randn_tensor((batch, C, draw, h, w), generator=generator, device=device, dtype=dtype)
+            if noise_type == "random":
+                return latents
+        else:
+            if latents.shape[2] == num_frames:
+                return latents.to(device)
+            if latents.shape[2] != L:
+                raise ValueError(f"latents hold {latents.shape[2]} frames: FreeNoise takes num_frames={num_frames} "
+                                 f"or context_length={L}")
+            latents = latents.to(device)
+        if latents.shape[2] < num_frames:  # repeat_context, or L user frames: tile
+            latents = torch.cat([latents] * (-(-num_frames // L)), dim=2)[:, :, :num_frames].contiguous()
+        if noise_type == "shuffle_context":
+            gens = generator if isinstance(generator, (list, tuple)) else [generator]
+            g0 = gens[0]
+            pdev = g0.device if g0 is not None else device
+            for i in range(L, num_frames, s):
+                start = max(0, i - L)
+                n = min(num_frames, start + s) - start
+                if n == 0:
+                    break
+                idx = (start + torch.randperm(n, generator=g0, device=pdev)).to(latents.device)
+                end = min(num_frames, i + n)
+                latents[:, :, i:end] = latents[:, :, idx[:end - i]]
+        return latents
 
     # ------------------------------------------------------------------ IP-Adapter
     def load_ip_adapter(self, pretrained_model_name_or_path_or_dict, subfolder=None,
@@ -483,7 +559,9 @@ class AnimateDiffPipeline:
         torch.manual_seed, a CUDA one from 01:103's torch.Generator("cuda")), in the pipeline's
         torch_dtype (float16 in the reference, 01:21 / 05:35; fp32 when the pipeline was loaded
         with torch_dtype=None, as diffusers draws in prompt_embeds.dtype), then moved."""
-        if latents is None:
+        if self.free_noise_enabled:
+            latents = self._prepare_latents_free_noise(batch, num_frames, h, w, generator=generator, latents=latents)
+        elif latents is None:
             shape = (batch, self.unet.config["in_channels"], num_frames, h, w)
             dtype = self.torch_dtype or torch.float32
             latents = randn_tensor(shape, generator=generator, device=self.unet.device, dtype=dtype)
@@ -497,6 +575,9 @@ class AnimateDiffPipeline:
                  ip_adapter_image=None, ip_adapter_image_embeds=None, **unused):
         if eta != 0.0:
             raise NotImplementedError("eta > 0")
+        if isinstance(prompt, dict) or isinstance(negative_prompt, dict):
+            raise NotImplementedError("a {frame: text} prompt dict (FreeNoise prompt travel) is not supported: "
+                                      "per-frame text embeddings need per-frame cross-attention K/V")
         if output_type not in ("latent", "pt", "np", "pil"):
             raise NotImplementedError(f"output_type {output_type!r}: use 'pil', 'pt', 'np' or 'latent'")
         if output_type != "latent" and self.vae is None:
@@ -656,6 +737,9 @@ class AnimateDiffVideoToVideoPipeline(AnimateDiffPipeline):
             raise NotImplementedError(f"output_type {output_type!r}: use 'pil', 'pt', 'np' or 'latent'")
         if video is None and latents is None:
             raise ValueError("video or latents required")
+        if isinstance(prompt, dict) or isinstance(negative_prompt, dict):
+            raise NotImplementedError("a {frame: text} prompt dict (FreeNoise prompt travel) is not supported: "
+                                      "per-frame text embeddings need per-frame cross-attention K/V")
         do_cfg = guidance_scale > 1
         if prompt_embeds is None:
             if prompt is None:
