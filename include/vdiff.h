@@ -322,7 +322,9 @@ int vd_attention_ex(const void* q, int64_t ldq, const void* k, int64_t ldk, cons
  *   *unit_scale  flash32 / flash40 / flash80: 1 when scale * log2(e) == 1 in fp32 and the
  *                instance without the per-score multiply runs; 0 for the other families
  *   *grid        workgroups of the (first) launch
- *   *exact_grid  VD_ATTN_K_FLASH40: workgroups of flash32's exact pass launched after it; else 0 */
+ *   *exact_grid  VD_ATTN_K_FLASH40: workgroups of flash32's exact pass launched after it (16 of its
+ *                128-query blocks each; a block reruns when flash40 left a NaN flag in the block's
+ *                own first output element, one flag per 128 queries); else 0 */
 enum {
   VD_ATTN_K_FLASH = 1,    /* the 16x16x32 flash kernel (plain, causal, tailed) */
   VD_ATTN_K_FLASH32 = 2,  /* d = 40 */

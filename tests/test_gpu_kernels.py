@@ -1022,6 +1022,261 @@ def _deferred_max_case(kind, sq=256, skv=640, d=40):
     return bf(q), bf(k), bf(v)
 
 
+LOG2E = math.log2(math.e)
+
+
+def _log2_scores(q, k, batch, heads, sq, skv, d, kv_div=1, scale=None):
+    """x = q.k * scale * log2(e) in fp64 on the operands as given (bf16-rounded), shaped
+    (batch, heads, sq, skv): the exponent of 2 the kernels work with."""
+    qd = q.double().reshape(batch, sq, heads, d).transpose(1, 2)
+    kd = k.double().reshape(batch // kv_div, skv, heads, d).transpose(1, 2).repeat_interleave(kv_div, 0)
+    return qd @ kd.transpose(-1, -2) * ((d ** -0.5 if scale is None else scale) * LOG2E)
+
+
+def _spike_preconditions(q, k, batch, heads, sq, skv, d, flagged, kv_div=1, scale=None):
+    """What makes a _spike_case one, from the fp64 scores alone (log2 units; m0 = a row's max over
+    keys 0..63, the first tile, which is where the fast passes of flash32 / flash40 take mu):
+      - every 256-query quarter of every flagged (b, h) has a row with max_{key >= 64} x - m0 >= 150.
+        Its fast-pass P there is >= 2^(150 - 1) (mu is m0 rounded to bf16; |m0| < 128 makes that
+        rounding < 1) > BAD = 2^100, so the quarter's row sum overflows whatever the other keys
+        add: flash32's 256-query workgroup takes its exact pass, and flash40 flags the 512-query
+        block around it — in these cases every quarter of a flagged head, so the same rows;
+      - every row of every other (b, h) has max x - m0 < 20, so l <= skv 2^21 < 2^32 (skv <= 1024):
+        neither a rescale nor an exact pass."""
+    assert skv <= 1024 and skv > 64
+    x = _log2_scores(q, k, batch, heads, sq, skv, d, kv_div, scale)
+    m0 = x[..., :64].amax(-1)
+    assert m0.abs().max().item() < 128
+    jump = x.amax(-1) - m0                                    # (batch, heads, sq), >= 0
+    late = x[..., 64:].amax(-1) - m0
+    for b in range(batch):
+        for h in range(heads):
+            if (b, h) in flagged:
+                for i in range((sq + 255) // 256):
+                    top = late[b, h, 256 * i:256 * (i + 1)].max().item()
+                    assert top >= 150, f"(b, h) = ({b}, {h}) quarter {i}: largest late jump {top:.1f} < 150"
+            else:
+                top = jump[b, h].max().item()
+                assert top < 20, f"quiet (b, h) = ({b}, {h}): jump {top:.1f} >= 20"
+
+
+def _spike_case(batch, heads, sq, skv, d, flagged, kv_div=1, dev="cuda"):
+    """bf16 q (batch sq, heads d) and k, v (batch / kv_div skv, heads d), column slices of wider
+    buffers (fused-QKV row strides), in which the heads of `flagged` — a collection of (b, h) —
+    overflow the fast pass of flash32 / flash40 in EVERY 256-query quarter and all others stay far
+    from any rescale (_spike_preconditions, asserted here from the fp64 scores).  Base values
+    q ~ N(0, 1), k ~ 0.1 N(0, 1), v ~ N(0, 1) from a seeded host generator: the same whatever
+    `flagged` is, so a quiet head's operands are bit-equal to those of the flagged = [] case.  For
+    quarter i of a flagged (b, h) one key row of that head in the last-but-one 64-key tile becomes
+    q_row S / |q_row|^2, q_row = query min(256 i + 37, sq - 1), with S = 180 sqrt(d) / log2 e: that
+    query's score on it is 180 in log2 units whatever |q_row| is (the other rows of the head see
+    it at about +-30 a sigma, also past every threshold, which is fine: the whole head is flagged).
+    With kv_div > 1 the key sits in the K the kv_div query batches share, so `flagged` has to list
+    (b, h) for all of them (asserted)."""
+    flagged = {(int(b), int(h)) for b, h in flagged}
+    for b, h in flagged:
+        assert 0 <= b < batch and 0 <= h < heads
+        assert all((b // kv_div * kv_div + j, h) in flagged for j in range(kv_div)), "flagged splits a shared K"
+    C, nq = heads * d, (sq + 255) // 256
+    g = torch.Generator().manual_seed(1000 * sq + skv + d)
+    qbuf = torch.randn(batch * sq, 3 * C, generator=g)
+    kvbuf = torch.randn(batch // kv_div * skv, 2 * C, generator=g)
+    kvbuf[:, :C] *= 0.1
+    qbuf, kvbuf = bf(qbuf), bf(kvbuf)
+    t0 = ((skv + 63) // 64 - 2) * 64                          # first key of the last-but-one tile
+    assert t0 >= 64 and 5 + 7 * (kv_div * nq - 1) < 64
+    S = 180.0 * math.sqrt(d) / LOG2E
+    for b, h in sorted(flagged):
+        for i in range(nq):
+            q_row = qbuf[b * sq + min(256 * i + 37, sq - 1), h * d:(h + 1) * d].float()
+            key = b // kv_div * skv + t0 + 5 + 7 * (b % kv_div * nq + i)
+            kvbuf[key, h * d:(h + 1) * d] = bf(q_row * (S / q_row.square().sum()))
+    qbuf, kvbuf = qbuf.to(dev), kvbuf.to(dev)
+    q, k, v = qbuf[:, :C], kvbuf[:, :C], kvbuf[:, C:]
+    _spike_preconditions(q, k, batch, heads, sq, skv, d, flagged, kv_div)
+    return q, k, v
+
+
+# (batch, heads, sq, skv, kv_div), the quiet (b, h) — every other one is flagged — for the exact
+# pass's 128-query blocks, ids (b heads + h) nqb + qblk with nqb = ceil(sq / 128), 16 per workgroup:
+#   A  nqb = 3, 18 blocks: the second workgroup holds 2; ids 15 | 16 are the two halves of quarter 0
+#      of (1, 2); the last half has 44 rows; quiet (0, 1) and (1, 0) sit among flagged blocks
+#   B  nqb = 5, 30 blocks: two flash40 blocks a head, the second a single quarter; ragged key tail;
+#      ids 15 | 16 are the halves of quarter 0 of (1, 0); quiet (0, 1) in the first workgroup,
+#      (1, 2) in the second
+#   C  nqb = 4 (the even control), K/V shared by two batches, 3 key tiles (below the automatic
+#      choice: flash40 forced); quiet (2, 1) and (3, 1) share a workgroup with flagged (2, 0), (3, 0)
+SPIKE_SHAPES = {"A": ((2, 3, 300, 640, 1), ((0, 1), (1, 0))),
+                "B": ((2, 3, 640, 333, 1), ((0, 1), (1, 2))),
+                "C": ((4, 2, 512, 192, 2), ((2, 1), (3, 1)))}
+_spike_cache = {}
+
+
+def _spike_shape(name, d=40, quiet_only=False):
+    """(shape, quiet, (q, k, v)) of a SPIKE_SHAPES entry, generated once and never written to;
+    quiet_only: the same base values with nothing flagged."""
+    shape, quiet = SPIKE_SHAPES[name]
+    if (name, d, quiet_only) not in _spike_cache:
+        batch, heads, sq, skv, kv_div = shape
+        flagged = [] if quiet_only else [(b, h) for b in range(batch) for h in range(heads) if (b, h) not in quiet]
+        _spike_cache[name, d, quiet_only] = _spike_case(batch, heads, sq, skv, d, flagged, kv_div)
+    return shape, quiet, _spike_cache[name, d, quiet_only]
+
+
+def _scale_variants(q, d):
+    """(q, scale) on the model's unit scale (softmax scale and log2 e folded into q) and prescaled."""
+    return (bf(q.float() * d ** -0.5 * LOG2E), 1.0 / LOG2E), (q, None)
+
+
+def _sliced_out(rows, C, out_f32):
+    """A NaN-filled (rows, C + 16) buffer and its column slice [8, 8 + C): ldo > heads d, rows
+    16-byte aligned."""
+    wide = torch.full((rows, C + 16), float("nan"), device="cuda", dtype=torch.float32 if out_f32 else BF)
+    return wide, wide[:, 8:8 + C]
+
+
+def _bits(t):
+    return t.contiguous().view(torch.int32 if t.dtype == torch.float32 else torch.int16)
+
+
+@pytest.mark.parametrize("out_f32", [False, True])
+@pytest.mark.parametrize("name", ["A", "B", "C"])
+def test_flash40_fixup_multi_block_bit_identical(cuda, name, out_f32):
+    """flash40's exact fix-up launch over several workgroups, several flagged blocks in each, and
+    quiet heads between them (SPIKE_SHAPES): batch and head offsets of the flag address, ldo >
+    heads d, bf16 and fp32 flags, a partly filled last workgroup, a ragged last 128-query block, a
+    K/V shared by two batches.  The output starts as NaN, so a block the fix-up skipped, or a flag
+    left behind, is not finite.  flash40 == flash32 bit for bit on both scales; the columns around
+    `out` keep their bytes; the quiet heads equal the call with nothing flagged bit for bit (their
+    operands are the same and a neighbour's fix-up must not touch them).
+    What this cannot show: while two 128-query halves shared one flag, a half was lost only when
+    its workgroup read the flag after another workgroup had finished re-running the other half — a
+    matter of launch timing that grids this small almost never produce, so this test is not
+    expected to fail on that protocol.  That race is closed by construction (a flag per block,
+    attention_flash32.hip) and reviewed there; what is pinned here is everything deterministic."""
+    (batch, heads, sq, skv, kv_div), quiet, (q, k, v) = _spike_shape(name)
+    _, _, (q0, k0, v0) = _spike_shape(name, quiet_only=True)
+    d, C = 40, heads * 40
+    flagged = [(b, h) for b in range(batch) for h in range(heads) if (b, h) not in quiet]
+    for (qq, sc), (qq0, _) in zip(_scale_variants(q, d), _scale_variants(q0, d)):
+        _spike_preconditions(qq, k, batch, heads, sq, skv, d, flagged, kv_div, sc)
+        _spike_preconditions(qq0, k0, batch, heads, sq, skv, d, [], kv_div, sc)
+        got = {}
+        for kern, (a, b, c) in (("flash40", (qq, k, v)), ("flash32", (qq, k, v)), ("calm", (qq0, k0, v0))):
+            wide, out = _sliced_out(batch * sq, C, out_f32)
+            before = wide.clone()
+            forced_attention("flash40" if kern == "calm" else kern, a, b, c, batch, heads, sq, skv, d, kv_div=kv_div,
+                             scale=sc, out=out, out_f32=out_f32)
+            assert torch.equal(_bits(wide[:, :8]), _bits(before[:, :8])), f"{kern}: columns left of out written"
+            assert torch.equal(_bits(wide[:, 8 + C:]), _bits(before[:, 8 + C:])), f"{kern}: columns right of out written"
+            got[kern] = out
+        a, b = got["flash40"], got["flash32"]
+        bad_rows = (~torch.isfinite(a.float())).any(1).nonzero().flatten()[:8].tolist()
+        assert not bad_rows, f"rows never recomputed (NaN left), first {bad_rows}"
+        assert torch.equal(_bits(a), _bits(b)), (a.float() - b.float()).abs().max().item()
+        for bq, h in quiet:
+            rows, cols = slice(bq * sq, (bq + 1) * sq), slice(h * d, (h + 1) * d)
+            assert torch.equal(_bits(a[rows, cols]), _bits(got["calm"][rows, cols])), f"quiet head ({bq}, {h}) moved"
+
+
+_spike_refs = {}
+
+
+def _spike_ref(name, d, unit):
+    """(q, scale, fp64 SDPA) of a spike shape on one scale, computed once."""
+    if (name, d, unit) not in _spike_refs:
+        (batch, heads, sq, skv, kv_div), quiet, (q, k, v) = _spike_shape(name, d)
+        qq, sc = _scale_variants(q, d)[0 if unit else 1]
+        _spike_preconditions(qq, k, batch, heads, sq, skv, d,
+                             [(b, h) for b in range(batch) for h in range(heads) if (b, h) not in quiet], kv_div, sc)
+        _spike_refs[name, d, unit] = qq, sc, sdpa_ref(qq, k, v, batch, heads, sq, skv, d, kv_div=kv_div, scale=sc)
+    return _spike_refs[name, d, unit]
+
+
+@pytest.mark.parametrize("name", ["A", "B"])
+@pytest.mark.parametrize("kernel,d", [("flash40", 40), ("flash32", 40), ("v1", 40), ("flash40", 80)])
+def test_attention_spike_multi_block_matches_fp64(cuda, kernel, d, name):
+    """Every d = 40 path and flash80 (d = 80) on the multi-head spike shapes against fp64 SDPA, on
+    both scales, bf16 and fp32 outputs, at the bar of test_flash_attention_deferred_max (P is
+    rounded to bf16 before PV, whatever the output type): flash32's in-kernel exact pass and
+    flash80's rare branch with several workgroups entering and several not, flash40's fix-up
+    launch against an independent reference."""
+    (batch, heads, sq, skv, kv_div), _, (_, k, v) = _spike_shape(name, d)
+    for unit in (True, False):
+        qq, sc, want = _spike_ref(name, d, unit)
+        for out_f32 in (False, True):
+            _, out = _sliced_out(batch * sq, heads * d, out_f32)
+            forced_attention(kernel, qq, k, v, batch, heads, sq, skv, d, kv_div=kv_div, scale=sc, out=out,
+                             out_f32=out_f32)
+            assert torch.isfinite(out.float()).all()
+            close_bf16(out, want, abs_frac=2e-3 * v.float().abs().max().item() / want.abs().max().item())
+
+
+MIXED_KINDS = ("ramp", "creep", "late_spike", "huge_spike", "offset", "negative")
+_mixed_cache = {}
+
+
+def _mixed_case(d, batch=2, heads=3, sq=300, skv=640):
+    """One _deferred_max_case kind per (b, h), MIXED_KINDS in (b heads + h) order, each single-head
+    construction in its head's columns.  The huge_spike head gets its spike once per 256-query
+    quarter (key skv - 70 + i = q_row S / |q_row|^2 for query min(256 i + 37, sq - 1), a score of
+    180 in log2 units) so that every quarter of it overflows the fast pass."""
+    if d not in _mixed_cache:
+        C = heads * d
+        q = torch.empty(batch * sq, C, device="cuda", dtype=BF)
+        k = torch.empty(batch * skv, C, device="cuda", dtype=BF)
+        v = torch.empty(batch * skv, C, device="cuda", dtype=BF)
+        for n, kind in enumerate(MIXED_KINDS):
+            b, h = divmod(n, heads)
+            qh, kh, vh = _deferred_max_case(kind, sq, skv, d)
+            if kind == "huge_spike":
+                for i in range((sq + 255) // 256):
+                    q_row = qh[min(256 * i + 37, sq - 1)].float()
+                    kh[skv - 70 + i] = bf(q_row * (180.0 * math.sqrt(d) / LOG2E / q_row.square().sum()))
+            q[b * sq:(b + 1) * sq, h * d:(h + 1) * d] = qh
+            k[b * skv:(b + 1) * skv, h * d:(h + 1) * d] = kh
+            v[b * skv:(b + 1) * skv, h * d:(h + 1) * d] = vh
+        _mixed_cache[d] = q, k, v
+    return _mixed_cache[d]
+
+
+@pytest.mark.parametrize("kernel,d", [("flash40", 40), ("flash32", 40), ("v1", 40), ("flash40", 80)])
+def test_deferred_max_patterns_mixed_per_head(cuda, kernel, d):
+    """The six deferred-max score patterns in ONE call, a different one per (b, h) at batch 2,
+    heads 3, sq 300, skv 640: neighbouring workgroups take different data-dependent branches, and
+    each has to find its own head's K/V and flags.  Each path within the deferred-max bar of fp64
+    on both scales.  At d = 40 the fp64 scores also say which heads overflow the fast pass — every
+    quarter of the huge_spike head jumps >= 150 past m0 (the first tile's max); every row of the
+    others has sum_j 2^(x_j - m0) < 2^98, and the fast pass's l can only be smaller than that
+    (its mu starts at m0 rounded to bf16, < 1 away, and only moves up; P's rounding adds 2^-8) —
+    so flash40 takes its fix-up launch for that head alone and is bit-identical to flash32."""
+    batch, heads, sq, skv = 2, 3, 300, 640
+    q, k, v = _mixed_case(d)
+    for qq, sc in _scale_variants(q, d):
+        want = sdpa_ref(qq, k, v, batch, heads, sq, skv, d, scale=sc)
+        got = forced_attention(kernel, qq, k, v, batch, heads, sq, skv, d, scale=sc)
+        assert torch.isfinite(got.float()).all()
+        close_bf16(got, want, abs_frac=2e-3 * v.float().abs().max().item() / want.abs().max().item())
+        if d == 40 and kernel == "flash40":
+            x = _log2_scores(qq, k, batch, heads, sq, skv, d, scale=sc)
+            m0 = x[..., :64].amax(-1, keepdim=True)
+            assert m0.abs().max().item() < 128
+            late = (x[..., 64:] - m0).amax(-1)
+            l_log2 = torch.logsumexp((x - m0) * math.log(2.0), -1) / math.log(2.0)
+            for n, kind in enumerate(MIXED_KINDS):
+                b, h = divmod(n, heads)
+                if kind == "huge_spike":
+                    for i in range((sq + 255) // 256):
+                        top = late[b, h, 256 * i:256 * (i + 1)].max().item()
+                        assert top >= 150, f"huge_spike quarter {i}: largest late jump {top:.1f} < 150"
+                else:
+                    top = l_log2[b, h].max().item()
+                    print(f"{kind}: log2 of the largest fast-pass row-sum bound {top:.1f}")
+                    assert top < 98, f"{kind}: row sum bound 2^{top:.1f} reaches the exact pass's trigger"
+            ref = forced_attention("flash32", qq, k, v, batch, heads, sq, skv, d, scale=sc)
+            assert torch.equal(got, ref), (got.float() - ref.float()).abs().max().item()
+
+
 @pytest.mark.parametrize("kind", ["ramp", "creep", "late_spike", "huge_spike", "offset", "negative"])
 def test_flash_attention_deferred_max(attn_path, kind):
     q, k, v = _deferred_max_case(kind)

@@ -63,7 +63,7 @@ COVERAGE = {
     "vd_layernorm": ("test_layer_norm",),
     "vd_attention": ("test_attention_abi_entry_points",),
     "vd_attention_f32": ("test_attention_abi_entry_points",),
-    "vd_attention_ex": ("test_attention",),
+    "vd_attention_ex": ("test_attention", "test_attention_flash40_fixup"),
     "vd_attention_plan": "no launch: a plan query",
     "vd_temporal_attention": ("test_temporal_attention",),
     "vd_temporal_attention_valu": ("test_temporal_attention",),
@@ -893,6 +893,35 @@ def test_attention(cuda, slack, out_f32, d, sq, skv, kern):
         assert torch.all(err <= 1e-4 + 1e-3 * want.abs()), err.max().item()
     else:
         close_bf16(got, sdpa_ref(qf, k, v, batch, heads, sq, skv, d, kv_div=kv_div))
+
+
+@pytest.mark.parametrize("slack", SLACKS)
+@pytest.mark.parametrize("out_f32", [False, True])
+def test_attention_flash40_fixup(cuda, slack, out_f32):
+    """flash40's NaN flags and flash32's exact fix-up launch inside poisoned frames, on spike shape
+    A of tests/test_gpu_kernels.py (batch 2, heads 3, sq 300, skv 640; four of the six heads
+    overflow the fast pass in every 256-query quarter): a flag per 128 queries must land inside
+    `out`, the fix-up's second workgroup holds 2 of 16 blocks, and its last block has 44 rows.
+    Frames intact, `out` written everywhere (a flagged block the fix-up skipped keeps its poison),
+    the result within the deferred-max bar of fp64 SDPA.  As in test_attention, an `out` whose
+    rows are not 16-byte ones (the odd slack, bf16) goes to the 16x16x32 kernel instead."""
+    from test_gpu_kernels import _spike_shape
+
+    (batch, heads, sq, skv, kv_div), _, (qf, kf, vf) = _spike_shape("A")
+    d, C = 40, heads * 40
+
+    def fn(mk):
+        q, k, v = mk.rows(qf, "q"), mk.rows(kf, "k"), mk.rows(vf, "v")
+        out = mk.out((batch * sq, C), F32 if out_f32 else BF)
+        kw = dict(kv_div=kv_div, out=out, out_f32=out_f32, kernel="flash40")
+        rows16 = out.data_ptr() % 16 == 0 and out.stride(0) * out.element_size() % 16 == 0
+        assert ops.attention_plan(q, k, v, batch, heads, sq, skv, d, **kw).family == ("flash40" if rows16 else "flash")
+        ops.attention(q, k, v, batch, heads, sq, skv, d, **kw)
+        return out
+
+    (got,) = run(fn, slack)
+    want = sdpa_ref(qf, kf, vf, batch, heads, sq, skv, d, kv_div=kv_div)
+    close_bf16(got, want, abs_frac=2e-3 * vf.float().abs().max().item() / want.abs().max().item())
 
 
 @pytest.mark.parametrize("out_f32", [False, True])

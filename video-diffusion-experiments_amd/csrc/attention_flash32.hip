@@ -255,15 +255,18 @@ __device__ __forceinline__ bool f32_loop(bf16_t* lds, const bf16_t* kb_ptr, cons
 
 // QB = 32-query blocks per wave: 2 (256 VGPRs, two waves per SIMD; one block per wave with three
 // waves per SIMD measured slower, 1010 vs 878 us: profiles/r02_attn_occupancy_ab.txt).
-// FIX: flash40's exact fix-up pass — a block whose first output element is a NaN flag (flash40
-// found a score jump past its fast pass's range there) recomputes its 256 queries with the exact
-// pass.  Round 6: one workgroup per F32_FIXW blocks (fix_blocks in all), whose first F32_FIXW
-// lanes read those blocks' flags at once (one load latency) and which then recomputes the flagged
-// ones in turn — the launch that follows every flash40 call was one workgroup per block, 4096 at
-// the level-1 self-attention, ~8 us with nothing flagged.  The fix-up runs QB = 1 (128-query
-// blocks, two per flagged quarter; a query's exact-pass arithmetic does not depend on QB): the
-// block loop at QB = 2's 256 VGPRs spilled.  Both halves of a quarter sit in one workgroup
-// (F32_FIXW even) and every flag is read before any block overwrites one.
+// FIX: flash40's exact fix-up pass — a 128-query block whose first output element is a NaN flag
+// (flash40 found a score jump past its fast pass's range in the 512-query block around it)
+// recomputes its queries with the exact pass.  Round 6: one workgroup per F32_FIXW blocks
+// (fix_blocks in all), whose first F32_FIXW lanes read those blocks' flags at once (one load
+// latency) and which then recomputes the flagged ones in turn — the launch that follows every
+// flash40 call was one workgroup per block, 4096 at the level-1 self-attention, ~8 us with
+// nothing flagged.  The fix-up runs QB = 1 (128-query blocks; a query's exact-pass arithmetic
+// does not depend on QB): the block loop at QB = 2's 256 VGPRs spilled.  Every block has a flag
+// of its own (flash40 writes one per 128 queries) and stores only its own rows, so the only
+// block that overwrites a flag is the one that read it: which blocks share a workgroup, and the
+// order the workgroups run in, do not matter (block ids start at an odd offset for every other
+// head when ceil(sq / 128) is odd).
 template <int D, bool UNITC, bool FIX = false, int QB = 2>
 __global__ __launch_bounds__(NT, 2) void flash32_kernel(
     const bf16_t* __restrict__ q, int64_t ldq, const bf16_t* __restrict__ k, int64_t ldk,
@@ -278,11 +281,11 @@ __global__ __launch_bounds__(NT, 2) void flash32_kernel(
   // consecutive logical ids and xcd_remap keeps consecutive ids on one XCD, so
   // that head's K/V is fetched into one L2 instead of eight.
   const int nqb = (int)((sq + 4 * 32 * QB - 1) / (4 * 32 * QB));
-  auto flag_of = [&](int64_t lid) {  // the block's flag: a NaN in the first output element of its
-    const int qblk = (int)(lid % nqb);  // flash40 256-query quarter
+  auto flag_of = [&](int64_t lid) {  // the block's own flag: a NaN in its first output element
+    const int qblk = (int)(lid % nqb);  // (first query of the block < sq, d 0 of its head)
     const int h = (int)((lid / nqb) % heads);
     const int64_t b = (lid / nqb) / heads;
-    const int64_t f = (b * sq + (((int64_t)qblk * (4 * 32 * QB)) & ~(int64_t)255)) * ldo + (int64_t)h * D;
+    const int64_t f = (b * sq + (int64_t)qblk * (4 * 32 * QB)) * ldo + (int64_t)h * D;
     return out_f32 ? __builtin_isnan(((const float*)o)[f]) : ((o[f] & 0x7FFF) > 0x7F80);
   };
   auto block = [&](int lid) {

@@ -339,9 +339,10 @@ __device__ __forceinline__ bool f4_loop(const char* smem, uint32_t lds0, const F
 }
 
 // One workgroup's whole block: Q' load, DMA setup, the fast pass, the epilogue.  When a score
-// jumped > ~100 (log2) past mu somewhere in the block it stores NaN flags instead, and flash32's
-// exact pass (flash32_kernel<..., FIX>, launched right after) recomputes the flagged quarters —
-// the exact loop inlined here as well would double the kernel's register pressure.
+// jumped > ~100 (log2) past mu somewhere in the block it stores NaN flags instead, one per
+// 128 queries, and flash32's exact pass (flash32_kernel<..., FIX>, launched right after)
+// recomputes every flagged 128-query block — the exact loop inlined here as well would double
+// the kernel's register pressure.
 template <bool UNITC>
 __device__ __forceinline__ bool f4_block(char* smem, const bf16_t* __restrict__ q, int64_t ldq,
                                          const bf16_t* __restrict__ k, int64_t ldk, const bf16_t* __restrict__ v,
@@ -420,10 +421,11 @@ __device__ __forceinline__ bool f4_block(char* smem, const bf16_t* __restrict__ 
   f32x16 oacc[2][QB];
   if (__syncthreads_or(f4_loop<UNITC>(smem, lds0, dma, issuer, g0, skv, qf, oacc, kl0, v0l, v1l, hh, c))) {
     // a score jumped > ~100 (log2) past mu somewhere in the block: no output here; a NaN in
-    // element (first query, d 0) of each 256-query quarter tells flash32's exact fix-up pass,
-    // launched right after, to recompute that quarter
+    // element (first query, d 0) of each 128-query half-quarter that starts below sq tells
+    // flash32's exact fix-up pass, launched right after, to recompute those 128 queries — one
+    // flag per fix-up block, so no two of its blocks share (or overwrite) a flag
     if (tid == 0)
-      for (int64_t qs = (int64_t)qblk * F4_QWG; qs < (int64_t)(qblk + 1) * F4_QWG && qs < sq; qs += 256) {
+      for (int64_t qs = (int64_t)qblk * F4_QWG; qs < (int64_t)(qblk + 1) * F4_QWG && qs < sq; qs += 128) {
         if (out_f32) ((float*)o)[(b * sq + qs) * ldo + (int64_t)h * D] = __builtin_nanf("");
         else o[(b * sq + qs) * ldo + (int64_t)h * D] = 0x7FC0;
       }

@@ -83,7 +83,7 @@ __device__ __forceinline__ void f80_loop(const char* smem, uint32_t lds0, const 
 #pragma unroll
     for (int i = 0; i < 16; ++i) oacc[db][i] = 0.f;
   float mu = 0.f;
-  const int T = (int)((skv + KT - 1) / KT);  // >= 4 (launch condition)
+  const int T = (int)((skv + KT - 1) / KT);  // >= 2 (launch condition; automatic from 4)
   constexpr float PTHR = 64.0f;  // 2^F32_THR: a P above it = a score THR past mu
 
   f32x16 s[2];
