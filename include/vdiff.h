@@ -575,6 +575,41 @@ int vd_block_transpose(const void* src, void* dst, int64_t nb, int64_t na, int64
  *   VD_EINVAL for both: s < 1 or s > L, L < 1 or L > 32, F < L, rows not a multiple of F * hw,
  *   x NULL, out == x (so a plain op 4 or 5, which carries s = 0, is refused), any bit above the
  *   low byte on ops 0-3; op 5 with y NULL, misaligned or y_f32 != 1; op 4 with y or y_f32 set.
+ *   Op 6, VD_ROWS_SPECTRAL, is FreeInit's frequency mix (diffusers' FreeInitMixin
+ *   _apply_freq_filter: ifftn(ifftshift(fftshift(fftn(x)) * lpf + fftshift(fftn(noise)) * (1 - lpf))).real
+ *   over (frames, height, width)), riding here for the same reason as ops 2-5.  By linearity it is
+ *     out = noise + Re(IDFT3(M * DFT3(x - noise))),
+ *   M the mask in un-shifted (DFT index) order; taking the real part equals using the
+ *   Hermitian-even part of M, so with a Hermitian-even table only the half spectrum kw <= W / 2
+ *   is held.  Unlike ops 0-5 ALL DATA ARE FP32 and C % 8 is not required.  The transform is split
+ *   into five axis passes, op = VD_ROWS_SPECTRAL | VD_ROWS_SPEC_PASS(p), p = 1..5 (the low byte is
+ *   the op), so that the complex scratch is the caller's and travels through the pointer slots:
+ *   the library still allocates nothing, never synchronises, and every pass is graph-capturable.
+ *   Geometry, the same in every pass: F = y_period frames, H = y_div, W = C, rows = n_vol * F * H
+ *   rows of W points, Wh = W / 2 + 1.  S is the scratch: rows rows of 2 * Wh floats, (re, im)
+ *   pairs, row stride >= 2 * Wh and even.
+ *     p = 1  S[r][kw] = sum_w (x[r][w] - y[r][w]) e^(-2 pi i w kw / W): x the rows to filter, y the
+ *            noise rows (y_f32 = 1, ldy its stride), out = S.
+ *     p = 2  forward DFT along H, in place: x = out = S (ldx == ldo), y NULL, y_f32 = 0.
+ *     p = 3  forward DFT along F, times the table, inverse DFT along F, in one launch, in place:
+ *            x = out = S; y the table [F][H][Wh] fp32, contiguous (y_f32 = 1, ldy = Wh), in
+ *            un-shifted order and Hermitian-even, M(k) == M(-k mod N) -- the caller's duty, the
+ *            entry point cannot check device values.
+ *     p = 4  inverse DFT along H, in place, as p = 2.
+ *     p = 5  out[r][w] = y[r][w] + (sum_kw m_kw Re(S[r][kw] e^(2 pi i kw w / W))) / (F H W), m = 2
+ *            for the bins whose mirror is not stored, else 1: x = S, y the noise rows, out the result
+ *            rows.  One correctly rounded division, one addition: a zero spectrum returns y.
+ *   Direct O(N^2) DFTs out of LDS.  Twiddles are cos / sin(2 pi ((j k) mod N) / N), the product
+ *   reduced mod N in integers, the value rounded once to fp32 from double precision.  A point is
+ *   four interleaved fp32 partial sums (n mod 4, ascending n, fmaf per term) combined as
+ *   (s0 + s1) + (s2 + s3); no atomics.  A volume's result depends on (F, H, W) and its own data
+ *   alone, never on n_vol, the volume's index, the row strides or what the scratch held before.
+ *   Sizes: 1 <= F, H, W <= VD_SPECTRAL_MAX (256) each, odd and non-power-of-two included.
+ *   VD_EINVAL, before any launch: p outside 1..5 (a plain op 6 carries p = 0; any bit above the
+ *   pass byte makes p > 5); a size outside the limit; rows not a multiple of F * H; x or out NULL
+ *   or not 16-byte aligned; out == x on p = 1, 5; out != x or ldo != ldx on p = 2..4; y NULL, not
+ *   16-byte aligned or y_f32 != 1 on p = 1, 3, 5; y or y_f32 set on p = 2, 4; ldy != Wh on p = 3;
+ *   a row stride shorter than its row (W for x / y / out rows, 2 * Wh for S) or an odd S stride.
  * vd_upsample_nearest2x: rows of n_img h x w images -> rows of their nearest x2 upsample
  *   (Upsample2D's F.interpolate(scale_factor=2.0, mode="nearest")). */
 enum {
@@ -583,9 +618,12 @@ enum {
   VD_ROWS_FREEU_FILTER = 2,
   VD_ROWS_SCALE = 3,
   VD_ROWS_WIN_GATHER = 4,
-  VD_ROWS_WIN_MERGE = 5
+  VD_ROWS_WIN_MERGE = 5,
+  VD_ROWS_SPECTRAL = 6
 };
 #define VD_ROWS_WIN_STRIDE(s) ((s) << 8)
+#define VD_ROWS_SPEC_PASS(p) ((p) << 8)
+#define VD_SPECTRAL_MAX 256
 int vd_rows_eltwise(int32_t op, const void* x, int64_t ldx, const void* y, int64_t ldy, int32_t y_f32,
                     int64_t y_div, int64_t y_period, int64_t rows, int64_t C, void* out, int64_t ldo,
                     vd_stream_t stream);

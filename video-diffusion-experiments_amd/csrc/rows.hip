@@ -310,9 +310,18 @@ inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace
 
+// op 6, FreeInit's spectral low-pass: fp32 volumes and rules of its own (spectral.hip)
+namespace vdrows __attribute__((visibility("hidden"))) {
+int spectral_launch(int32_t pass, const void* x, int64_t ldx, const void* y, int64_t ldy, int32_t y_f32, int64_t H,
+                    int64_t F, int64_t rows, int64_t W, void* out, int64_t ldo, vd_stream_t stream);
+}
+
 extern "C" int vd_rows_eltwise(int32_t op, const void* x, int64_t ldx, const void* y, int64_t ldy, int32_t y_f32,
                                int64_t y_div, int64_t y_period, int64_t rows, int64_t C, void* out, int64_t ldo,
                                vd_stream_t stream) {
+  // op 6 carries its pass above the low byte (VD_ROWS_SPEC_PASS); none of the bf16 rules below apply
+  if (op >= 0 && (op & 0xff) == VD_ROWS_SPECTRAL)
+    return vdrows::spectral_launch(op >> 8, x, ldx, y, ldy, y_f32, y_div, y_period, rows, C, out, ldo, stream);
   // ops 4 and 5 carry the window stride above the low byte (VD_ROWS_WIN_STRIDE); no other op does
   const int32_t win_s = op >> 8;
   const bool win = op >= 0 && ((op & 0xff) == VD_ROWS_WIN_GATHER || (op & 0xff) == VD_ROWS_WIN_MERGE);

@@ -903,6 +903,99 @@ def window_merge(xw, wt_dev, B, F, hw, L, s, out=None):
     return out
 
 
+ROWS_SPECTRAL = 6            # VD_ROWS_SPECTRAL
+ROWS_SPEC_PASS_SHIFT = 8     # VD_ROWS_SPEC_PASS(p) = p << 8, p in 1..5
+SPECTRAL_MAX = 256           # VD_SPECTRAL_MAX: the longest F, H or W
+FREE_INIT_METHODS = ("butterworth", "gaussian", "ideal")
+
+
+def free_init_mask(F, H, W, method, order, spatial_stop_frequency, temporal_stop_frequency):
+    """diffusers' FreeInitMixin._get_free_init_freq_filter over (F, H, W) in fp64, indexed in
+    fftshift-ed order (centred at N / 2): all zeros when a stop frequency is 0."""
+    ds, dt = float(spatial_stop_frequency), float(temporal_stop_frequency)
+    if method not in FREE_INIT_METHODS:
+        raise NotImplementedError("`filter_type` must be one of gaussian, butterworth or ideal")
+    if ds == 0 or dt == 0:
+        return torch.zeros(F, H, W, dtype=torch.float64)
+    t = torch.arange(F, dtype=torch.float64)[:, None, None]
+    h = torch.arange(H, dtype=torch.float64)[None, :, None]
+    w = torch.arange(W, dtype=torch.float64)[None, None, :]
+    d2 = ((ds / dt) * (2 * t / F - 1)) ** 2 + (2 * h / H - 1) ** 2 + (2 * w / W - 1) ** 2
+    if method == "butterworth":
+        return 1 / (1 + (d2 / ds ** 2) ** order)
+    if method == "gaussian":
+        return torch.exp(-1 / (2 * ds ** 2) * d2)
+    return (d2 <= ds * 2).to(torch.float64)
+
+
+def free_init_table(F, H, W, method="butterworth", order=4, spatial_stop_frequency=0.25,
+                    temporal_stop_frequency=0.25, device=None, dtype=torch.float32):
+    """The operand of free_init_filter: diffusers' mask in fp64, ifftshift-ed to DFT index order,
+    made Hermitian-even, M_s(k) = (M(k) + M(-k mod N)) / 2 (what taking the real part of the
+    inverse transform amounts to; M is already even when F, H and W are all even), cut to the half
+    spectrum [F][H][W // 2 + 1] and rounded once to fp32 (dtype=torch.float64 keeps the unrounded
+    table, for checking the identity).  Pure torch: runs on the CPU too."""
+    m = free_init_mask(F, H, W, method, order, spatial_stop_frequency, temporal_stop_frequency)
+    m = torch.fft.ifftshift(m, dim=(0, 1, 2))
+    mirror = m.flip(0, 1, 2).roll((1, 1, 1), (0, 1, 2))  # M(-k mod N)
+    m = (m + mirror) / 2
+    return m[:, :, :W // 2 + 1].contiguous().to(dtype).to(device or "cpu")
+
+
+def free_init_filter(z, noise, table, out=None, scratch=None):
+    """FreeInit's frequency mix (diffusers' _apply_freq_filter) of fp32 (..., F, H, W) tensors: the
+    low spatio-temporal frequencies of z, the high ones of noise, the leading dims being the
+    volumes; out = noise + Re(IDFT3(table * DFT3(z - noise))) in five launches of vd_rows_eltwise
+    op 6 on the current stream.  table: free_init_table(F, H, W, ...) on the device.  scratch: fp32,
+    n_vol * F * H * 2 * (W // 2 + 1) elements, allocated when None; what it holds does not matter."""
+    _dev(z, noise, table, out, scratch)
+    if z.dim() < 3:
+        raise ValueError(f"free_init_filter z: expected (..., F, H, W), got shape {tuple(z.shape)}")
+    F, H, W = z.shape[-3:]
+    Wh = W // 2 + 1
+    for name, t in (("z", z), ("noise", noise), ("table", table)):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError(f"free_init_filter {name}: expected a contiguous fp32 tensor, got {t.dtype}, "
+                             f"strides {t.stride()}")
+    if noise.shape != z.shape:
+        raise ValueError(f"free_init_filter noise: shape {tuple(noise.shape)} is not z's {tuple(z.shape)}")
+    if tuple(table.shape) != (F, H, Wh):
+        raise ValueError(f"free_init_filter table: shape {tuple(table.shape)} is not ({F}, {H}, {Wh}) "
+                         "(ops.free_init_table)")
+    if max(F, H, W) > SPECTRAL_MAX:
+        raise ValueError(f"free_init_filter: F, H, W = {F}, {H}, {W} exceed the kernel's limit of {SPECTRAL_MAX} each")
+    rows = z.numel() // W
+    if rows == 0:
+        raise ValueError("free_init_filter z: empty tensor")
+    if out is None:
+        out = torch.empty_like(z)
+    if out.dtype != torch.float32 or out.shape != z.shape or not out.is_contiguous():
+        raise ValueError(f"free_init_filter out: expected a contiguous fp32 tensor of shape {tuple(z.shape)}, got "
+                         f"{out.dtype} {tuple(out.shape)}")
+    if scratch is None:
+        scratch = torch.empty(rows * 2 * Wh, device=z.device, dtype=torch.float32)
+    if scratch.dtype != torch.float32 or scratch.numel() < rows * 2 * Wh or not scratch.is_contiguous():
+        raise ValueError(f"free_init_filter scratch: expected {rows * 2 * Wh} contiguous fp32 elements, got "
+                         f"{scratch.dtype} x {scratch.numel()}")
+    for name, t in (("z", z), ("noise", noise), ("table", table), ("out", out), ("scratch", scratch)):
+        if t.data_ptr() % 16:
+            raise ValueError(f"free_init_filter {name}: the base is not 16-byte aligned (a view into a larger "
+                             "tensor? pass a clone)")
+    if out.data_ptr() in (z.data_ptr(), noise.data_ptr()):
+        raise ValueError("free_init_filter out: must not be z or noise (the last pass reads noise as it writes)")
+    fn, st, S = lib().vd_rows_eltwise, _stream(), _p(scratch)
+
+    def op(p):
+        return ROWS_SPECTRAL | (p << ROWS_SPEC_PASS_SHIFT)
+
+    check(fn(op(1), _p(z), W, _p(noise), W, 1, H, F, rows, W, S, 2 * Wh, st), "vd_rows_eltwise(spectral 1)")
+    check(fn(op(2), S, 2 * Wh, None, 0, 0, H, F, rows, W, S, 2 * Wh, st), "vd_rows_eltwise(spectral 2)")
+    check(fn(op(3), S, 2 * Wh, _p(table), Wh, 1, H, F, rows, W, S, 2 * Wh, st), "vd_rows_eltwise(spectral 3)")
+    check(fn(op(4), S, 2 * Wh, None, 0, 0, H, F, rows, W, S, 2 * Wh, st), "vd_rows_eltwise(spectral 4)")
+    check(fn(op(5), S, 2 * Wh, _p(noise), W, 1, H, F, rows, W, _p(out), W, st), "vd_rows_eltwise(spectral 5)")
+    return out
+
+
 def upsample2x_rows(x, n_img, h, w, out=None):
     _dev(x, out)
     if out is None:

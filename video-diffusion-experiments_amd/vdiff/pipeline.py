@@ -39,6 +39,11 @@ there on).
 AnimateDiffVideoToVideoPipeline (diffusers' second AnimateDiff pipeline) starts the same loop
 from a video: the frames are encoded by the VAE encoder (`AutoencoderKL(..., encoder=True)`),
 noised to the timestep `strength` picks, and denoised over the remaining timesteps.
+
+FreeInit (diffusers' FreeInitMixin, `enable_free_init`) wraps the loop of both pipelines: the video
+is sampled num_iters times on ONE DenoiseLoop and one captured graph (`DenoiseLoop.reschedule`
+swaps in the shorter schedules of use_fast_sampling), and between two runs the latents are noised
+back with the initial noise and low-pass mixed with fresh noise by `ops.free_init_filter`.
 """
 from __future__ import annotations
 
@@ -95,7 +100,9 @@ class DenoiseLoop:
         self.Bt = self.ncfg * self.B
         self.cfg_shard = cfg_shard if self.ncfg == 2 else None
         ts = scheduler.timesteps if timesteps is None else timesteps
+        self.scheduler = scheduler
         self.n_steps = len(ts)
+        self.capacity = len(ts)  # rows of the device tables: the longest schedule reschedule() takes
         self.ts = torch.as_tensor(ts).to(dev, torch.float32)
         self.coef = scheduler.coefficient_table(torch.as_tensor(ts).cpu()).to(dev)
         # the scheduler's fused CFG+update kernel; Euler's also applies the next step's
@@ -171,6 +178,24 @@ class DenoiseLoop:
         self.step_idx.zero_()
         self.issued = 0
         ops.pack_latents(self.lat, dup=self.ncfg, cpad=CIN_PAD, out=self.x_in2, in_div=self.in_div0)
+
+    def reschedule(self, timesteps):
+        """Switch to another schedule of at most `capacity` steps without a new capture: its
+        timesteps and coefficient rows go into the prefix of the same device tables, which the
+        step's launches (and so the captured graph) read by pointer at the device step index.
+        scheduler.set_timesteps must already hold the schedule the timesteps come from (Euler's
+        coefficients are looked up in it).  reset(latents) must follow before the next run()."""
+        ts = torch.as_tensor(timesteps)
+        n = len(ts)
+        if n < 1 or n > self.capacity:
+            raise ValueError(f"reschedule: {n} timesteps, the loop's tables were built for 1..{self.capacity}")
+        self.ts[:n].copy_(ts.to(self.ts.device, torch.float32))
+        self.coef[:n].copy_(self.scheduler.coefficient_table(ts.cpu()).to(self.coef.device))
+        if self.kind == "euler":
+            self.in_div0 = self.scheduler.input_divisor(self.scheduler.index_for_timestep(float(ts[0])))
+        self.n_steps = n
+        self.issued = n  # nothing may run before reset()
+        return self
 
     def prime(self):
         """One eager step (loads kernels, fills the cross-attention K/V cache,
@@ -265,6 +290,7 @@ class AnimateDiffPipeline:
         self.feature_extractor = None
         self.image_projection = None
         self._free_noise = None  # (context_length, context_stride, noise_type) while FreeNoise is enabled
+        self._free_init_num_iters = None  # enable_free_init's arguments while FreeInit is enabled
         # the dtype the initial noise is drawn in (diffusers: prompt_embeds.dtype, i.e. the
         # pipeline's torch_dtype, fp32 when none is given); from_config keeps the reference's fp16
         self.torch_dtype = None
@@ -406,6 +432,89 @@ class AnimateDiffPipeline:
                 idx = (start + torch.randperm(n, generator=g0, device=pdev)).to(latents.device)
                 end = min(num_frames, i + n)
                 latents[:, :, i:end] = latents[:, :, idx[:end - i]]
+        return latents
+
+    # ------------------------------------------------------------------ FreeInit
+    def enable_free_init(self, num_iters=3, use_fast_sampling=False, method="butterworth", order=4,
+                         spatial_stop_frequency=0.25, temporal_stop_frequency=0.25):
+        """diffusers' FreeInitMixin.enable_free_init: __call__ samples the video num_iters times;
+        between two runs the finished latents are noised back to the last training timestep with
+        the initial noise and their high spatio-temporal frequencies replaced by fresh noise
+        through a 3-D low-pass over (frames, height, width) (ops.free_init_filter).
+        use_fast_sampling runs iteration i over max(1, int(steps / num_iters * (i + 1))) steps."""
+        if int(num_iters) != num_iters or num_iters < 1:
+            raise ValueError(f"num_iters must be an integer >= 1, got {num_iters!r}")
+        if method not in ops.FREE_INIT_METHODS:
+            raise NotImplementedError("`filter_type` must be one of gaussian, butterworth or ideal")
+        if int(order) != order or order < 1:
+            raise ValueError(f"order must be an integer >= 1, got {order!r}")
+        if spatial_stop_frequency < 0 or temporal_stop_frequency < 0:
+            raise ValueError(f"stop frequencies must be >= 0, got spatial_stop_frequency={spatial_stop_frequency}, "
+                             f"temporal_stop_frequency={temporal_stop_frequency}")
+        self._free_init_num_iters = int(num_iters)
+        self._free_init_use_fast_sampling = bool(use_fast_sampling)
+        self._free_init_method = method
+        self._free_init_order = int(order)
+        self._free_init_spatial_stop_frequency = spatial_stop_frequency
+        self._free_init_temporal_stop_frequency = temporal_stop_frequency
+
+    def disable_free_init(self):
+        self._free_init_num_iters = None
+
+    @property
+    def free_init_enabled(self) -> bool:
+        return getattr(self, "_free_init_num_iters", None) is not None
+
+    def _free_init_steps(self, num_inference_steps, iteration):
+        """The step count of one FreeInit iteration."""
+        if self._free_init_use_fast_sampling:
+            return max(1, int(num_inference_steps / self._free_init_num_iters * (iteration + 1)))
+        return num_inference_steps
+
+    def _apply_free_init(self, latents, iteration, num_inference_steps, generator=None):
+        """diffusers' FreeInitMixin._apply_free_init -> (latents, timesteps).  Iteration 0 keeps a
+        clone of the latents as the initial noise (and builds the call's filter table and
+        scratch); a later one returns
+          free_init_filter(add_noise(latents, initial_noise, num_train_timesteps - 1), z_rand),
+        z_rand one fp32 randn_tensor draw from `generator`.  Then scheduler.set_timesteps with the
+        iteration's step count."""
+        if iteration == 0:
+            F, H, W = latents.shape[-3:]
+            self._free_init_initial_noise = latents.detach().clone()
+            self._free_init_table = ops.free_init_table(
+                F, H, W, self._free_init_method, self._free_init_order, self._free_init_spatial_stop_frequency,
+                self._free_init_temporal_stop_frequency, device=latents.device)
+            self._free_init_scratch = torch.empty(latents.numel() // W * 2 * (W // 2 + 1), device=latents.device,
+                                                  dtype=torch.float32)
+        else:
+            t = self.scheduler.config.num_train_timesteps - 1
+            z_t = self.scheduler.add_noise(latents, self._free_init_initial_noise,
+                                           torch.full((latents.shape[0],), t)).to(torch.float32).contiguous()
+            z_rand = randn_tensor(latents.shape, generator=generator, device=latents.device, dtype=torch.float32)
+            latents = ops.free_init_filter(z_t, z_rand.contiguous(), self._free_init_table,
+                                           scratch=self._free_init_scratch)
+        self.scheduler.set_timesteps(self._free_init_steps(num_inference_steps, iteration))
+        return latents, self.scheduler.timesteps
+
+    def _free_init_sample(self, latents, num_inference_steps, generator, make_loop, schedule=lambda ts: ts):
+        """The FreeInit iterations around one DenoiseLoop: make_loop(timesteps) builds it, once, for
+        the longest schedule; schedule(timesteps) is what an iteration runs of its timesteps (the
+        video-to-video pipeline's cut by strength).  -> the last iteration's latents."""
+        n = self._free_init_num_iters
+        self.scheduler.set_timesteps(max(self._free_init_steps(num_inference_steps, i) for i in range(n)))
+        now = schedule(self.scheduler.timesteps)
+        loop = make_loop(now).prime()
+        try:
+            for i in range(n):
+                latents, ts = self._apply_free_init(latents, i, num_inference_steps, generator)
+                ts = schedule(ts)
+                if len(ts) != len(now) or not torch.equal(torch.as_tensor(ts).cpu(), torch.as_tensor(now).cpu()):
+                    loop.reschedule(ts)
+                    now = ts
+                loop.reset(latents)
+                latents = loop.run()
+        finally:
+            self._free_init_initial_noise = self._free_init_table = self._free_init_scratch = None
         return latents
 
     # ------------------------------------------------------------------ IP-Adapter
@@ -575,6 +684,9 @@ class AnimateDiffPipeline:
                  ip_adapter_image=None, ip_adapter_image_embeds=None, **unused):
         if eta != 0.0:
             raise NotImplementedError("eta > 0")
+        if self.free_init_enabled and self.dist is not None:
+            raise NotImplementedError("FreeInit with a frame-sharded pipeline (dist=) is not supported: the filter "
+                                      "needs every frame of a video and the ranks would have to agree on z_rand")
         if isinstance(prompt, dict) or isinstance(negative_prompt, dict):
             raise NotImplementedError("a {frame: text} prompt dict (FreeNoise prompt travel) is not supported: "
                                       "per-frame text embeddings need per-frame cross-attention K/V")
@@ -619,9 +731,15 @@ class AnimateDiffPipeline:
         if self.dist is not None:
             fl = self.dist.frames_local(num_frames)
             local = latents[:, :, self.dist.rank * fl:(self.dist.rank + 1) * fl]
-        loop = DenoiseLoop(self.unet, self.scheduler, local, ehs, guidance_scale,
-                           use_graph=use_graph, ip_embeds=ip_embeds).prime()
-        out = loop.run()
+        if self.free_init_enabled:
+            out = self._free_init_sample(
+                latents, num_inference_steps, generator,
+                lambda ts: DenoiseLoop(self.unet, self.scheduler, latents, ehs, guidance_scale, timesteps=ts,
+                                       use_graph=use_graph, ip_embeds=ip_embeds))
+        else:
+            loop = DenoiseLoop(self.unet, self.scheduler, local, ehs, guidance_scale,
+                               use_graph=use_graph, ip_embeds=ip_embeds).prime()
+            out = loop.run()
         if self.dist is not None:
             out = self.dist.all_gather_frames(out)
         if output_type != "latent":
@@ -733,6 +851,9 @@ class AnimateDiffVideoToVideoPipeline(AnimateDiffPipeline):
                  ip_adapter_image=None, ip_adapter_image_embeds=None, **unused):
         if eta != 0.0:
             raise NotImplementedError("eta > 0")
+        if self.free_init_enabled and self.dist is not None:
+            raise NotImplementedError("FreeInit with a frame-sharded pipeline (dist=) is not supported: the filter "
+                                      "needs every frame of a video and the ranks would have to agree on z_rand")
         if output_type not in ("latent", "pt", "np", "pil"):
             raise NotImplementedError(f"output_type {output_type!r}: use 'pil', 'pt', 'np' or 'latent'")
         if video is None and latents is None:
@@ -770,9 +891,16 @@ class AnimateDiffVideoToVideoPipeline(AnimateDiffPipeline):
         if self.dist is not None:  # every rank computed the same latents from the shared CPU generator
             fl = self.dist.frames_local(num_frames)
             local = latents[:, :, self.dist.rank * fl:(self.dist.rank + 1) * fl]
-        loop = DenoiseLoop(self.unet, self.scheduler, local, ehs, guidance_scale, timesteps=ts,
-                           use_graph=use_graph, ip_embeds=ip_embeds).prime()
-        out = loop.run()
+        if self.free_init_enabled:
+            out = self._free_init_sample(
+                latents, num_inference_steps, generator,
+                lambda t: DenoiseLoop(self.unet, self.scheduler, latents, ehs, guidance_scale, timesteps=t,
+                                      use_graph=use_graph, ip_embeds=ip_embeds),
+                schedule=lambda t: self.get_timesteps(len(t), strength)[0])
+        else:
+            loop = DenoiseLoop(self.unet, self.scheduler, local, ehs, guidance_scale, timesteps=ts,
+                               use_graph=use_graph, ip_embeds=ip_embeds).prime()
+            out = loop.run()
         if self.dist is not None:
             out = self.dist.all_gather_frames(out)
         if output_type != "latent":
