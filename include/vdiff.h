@@ -494,8 +494,24 @@ int vd_lpips_pairs(const void* frames_u8, int64_t videos, int32_t frames, int32_
  *   d = (x - x0)/s, x += d*(s_next - s)) and coef[4*step] = {sigma, sigma_next,
  *   sqrt(sigma_next^2 + 1), 0}; next_in = the next step's scale_model_input(x)
  *   packed to bf16 — §8f rank 2 (experiments/01_baseline_generation.py:76-80).
+ *   It refuses VD_STEP_LCM (VD_EINVAL).
+ * VD_STEP_LCM OR-ed into vd_ddim_cfg_step's ncfg (the low byte stays 1 or 2; any other bit above
+ *   it is VD_EINVAL): the diffusers LCMScheduler.step update (epsilon prediction) instead of DDIM's,
+ *     x0 = (x - sqrt(1-a_t) eps) / sqrt(a_t);  den = c_out*x0 + c_skip*x
+ *     x <- add_noise ? sqrt(a_prev)*den + sqrt(1-a_prev)*noise : den
+ *   with the same one-rounding-per-op fp32 arithmetic; x0_out receives den (diffusers' `denoised`),
+ *   next_in bf16(x) as above.  It rides on this entry point instead of a new symbol, as
+ *   VD_CONV_PAD_END and VD_ATTN_TAIL ride on theirs, and the signature has no spare pointer, so
+ *   the per-step noise travels in coef: one fp32 buffer, 16-byte aligned, of
+ *     n_coef rows of 8 floats {sqrt(a_t), sqrt(1-a_t), sqrt(a_prev), sqrt(1-a_prev), c_skip,
+ *       c_out, add_noise (0.0 or 1.0), 0}, then
+ *     n_coef slabs of B*C*F*H*W floats in (B,C,F,H,W) order, from float offset 8*n_coef.
+ *   Step st (= *step_idx clamped to the n_coef rows) reads row st and, only when that row's
+ *   add_noise != 0, slab st: the last step's slab is sized but never read.  Step index, branch
+ *   and noise are all read inside the launch, so a captured step replays over the whole schedule.
  * vd_step_advance: ++*step_idx (one thread; the last node of a captured step).
  */
+enum { VD_STEP_LCM = 0x100 }; /* OR-ed into vd_ddim_cfg_step's ncfg, see above */
 int vd_timestep_embed(const float* ts, int64_t n_ts, const int32_t* step_idx, int64_t B,
                       int32_t dim, void* out, vd_stream_t stream);
 int vd_pack_latents(const float* x, int64_t B, int64_t C, int64_t F, int64_t H, int64_t W,

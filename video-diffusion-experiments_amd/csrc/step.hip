@@ -8,7 +8,9 @@
 // reading the conv_out rows directly (NHWC fp32) and, optionally, writing the
 // next step's packed bf16 UNet input (the CFG cat([x, x])) in the same pass.
 // Coefficients come from a device table indexed by a device step counter so a
-// captured hipGraph of one step can be replayed for every timestep.
+// captured hipGraph of one step can be replayed for every timestep.  With VD_STEP_LCM in ncfg
+// the same entry point launches the LCMScheduler update, whose per-step noise follows the
+// coefficient rows in the same device buffer (lcm_cfg_kernel).
 #include "common.h"
 
 namespace {
@@ -164,6 +166,54 @@ __global__ void euler_cfg_kernel(const float* eps, int64_t ld_eps, int ncfg, flo
   }
 }
 
+// CFG combine + diffusers:LCMScheduler.step (epsilon prediction), in diffusers' fp32 operation
+// order (vd_ddim_cfg_step with VD_STEP_LCM in ncfg):
+//   x0 = (x - sqrt(1-a_t) eps) / sqrt(a_t);  den = c_out x0 + c_skip x
+//   x <- add_noise ? sqrt(a_p) den + sqrt(1-a_p) noise : den
+// coef holds n_coef rows of 8 floats {sqrt(a_t), sqrt(1-a_t), sqrt(a_p), sqrt(1-a_p), c_skip,
+// c_out, add_noise, 0} and, from float 8 * n_coef on, n_coef noise slabs of B*C*F*HW floats in
+// latent order.  Row, branch and noise are all read here by the device step index, so one
+// captured launch serves the whole schedule.  A slab whose row has add_noise == 0 is never read.
+__global__ void lcm_cfg_kernel(const float* eps, int64_t ld_eps, int ncfg, float g, float* lat,
+                               int64_t B, int64_t C, int64_t F, int64_t HW, const float* coef,
+                               int64_t n_coef, const int32_t* step_idx, float* x0_out, bf16_t* next_in,
+                               int64_t cpad) {
+#pragma clang fp contract(off)  // one rounding per operation, as torch's separate fp32 ops
+  const int st = table_row(step_idx, n_coef);
+  const float* row = coef + 8 * (int64_t)st;
+  const float sat = row[0], s1at = row[1], sap = row[2], s1ap = row[3];
+  const float c_skip = row[4], c_out = row[5];
+  const bool add_noise = row[6] != 0.f;
+  const int64_t total = B * C * F * HW;
+  const int64_t half_rows = B * F * HW;
+  const float* noise = coef + 8 * n_coef + (int64_t)st * total;
+  for (int64_t i = (int64_t)blockIdx.x * NT + threadIdx.x; i < total; i += (int64_t)gridDim.x * NT) {
+    const int64_t p = i % HW;
+    const int64_t f = (i / HW) % F;
+    const int64_t c = (i / (HW * F)) % C;
+    const int64_t b = i / (HW * F * C);
+    const int64_t r = (b * F + f) * HW + p;
+    float e = eps[r * ld_eps + c];
+    if (ncfg == 2) {
+      const float ec = eps[(r + half_rows) * ld_eps + c];
+      e = e + g * (ec - e);
+    }
+    const float x = lat[i];
+    const float x0 = div_rn(x - s1at * e, sat);
+    const float den = c_out * x0 + c_skip * x;
+    float xn = den;
+    if (add_noise) xn = sap * den + s1ap * noise[i];
+    lat[i] = xn;
+    if (x0_out) x0_out[i] = den;
+    if (next_in) {
+      const bf16_t v = f2bf(xn);
+      next_in[r * cpad + c] = v;
+      if (ncfg == 2) next_in[(r + half_rows) * cpad + c] = v;
+      if (c == 0) zero_pad_cols(next_in, r, half_rows, ncfg, C, cpad);
+    }
+  }
+}
+
 __global__ void step_advance_kernel(int32_t* step_idx) { *step_idx += 1; }
 
 __global__ void block_transpose_kernel(const bf16_t* src, bf16_t* dst, int64_t nb, int64_t na,
@@ -220,8 +270,18 @@ extern "C" int vd_ddim_cfg_step(const float* eps, int64_t ld_eps, int32_t ncfg, 
                                 float* latents, int64_t B, int64_t C, int64_t F, int64_t H,
                                 int64_t W, const float* coef, int64_t n_coef, const int32_t* step_idx,
                                 float* x0_out, void* next_in, int64_t cpad, vd_stream_t stream) {
+  // VD_STEP_LCM rides on ncfg above its low byte; any other high bit is refused
+  const bool lcm = (ncfg & VD_STEP_LCM) != 0;
+  if (lcm) ncfg &= ~VD_STEP_LCM;
   VD_CHECK_ARG(eps && latents && coef && n_coef > 0 && (ncfg == 1 || ncfg == 2) && ld_eps >= C);
   if (next_in) VD_CHECK_ARG(cpad >= C);
+  if (lcm) {
+    VD_CHECK_ARG(B > 0 && C > 0 && F > 0 && H > 0 && W > 0 && ((uintptr_t)coef & 15) == 0);
+    hipLaunchKernelGGL(lcm_cfg_kernel, dim3(grid_for(B * C * F * H * W)), dim3(NT), 0,
+                       (hipStream_t)stream, eps, ld_eps, ncfg, guidance, latents, B, C, F, H * W,
+                       coef, n_coef, step_idx, x0_out, (bf16_t*)next_in, cpad);
+    return vd_launch_status();
+  }
   hipLaunchKernelGGL(ddim_cfg_kernel, dim3(grid_for(B * C * F * H * W)), dim3(NT), 0,
                      (hipStream_t)stream, eps, ld_eps, ncfg, guidance, latents, B, C, F, H * W,
                      coef, n_coef, step_idx, x0_out, (bf16_t*)next_in, cpad);

@@ -16,6 +16,6 @@ from .pretrained import MotionAdapter  # noqa: F401
 from .pipeline import (AnimateDiffPipeline, AnimateDiffPipelineOutput,  # noqa: F401
                        AnimateDiffVideoToVideoPipeline, DenoiseLoop)
 from .sched import (DDIMScheduler, DDIMSchedulerOutput, EulerDiscreteScheduler,  # noqa: F401
-                    EulerDiscreteSchedulerOutput)
+                    EulerDiscreteSchedulerOutput, LCMScheduler, LCMSchedulerOutput)
 from .tokenizer import CLIPTokenizer  # noqa: F401
 from .weights import init_synthetic_, load_diffusers_state_dict  # noqa: F401

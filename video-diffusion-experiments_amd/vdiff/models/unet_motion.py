@@ -165,6 +165,31 @@ class UNetMotionModel(nn.Module):
         for a in self.spatial_cross_attentions():
             a.remove_ip_adapter()
 
+    # ------------------------------------------------------------------ LoRA
+    def load_lora_state_dict(self, state_dict, adapter_name=None, weight: float = 1.0):
+        """Merge a LoRA (any key layout of vdiff.lora) into the parameters as a new active adapter
+        and re-pack the operands; -> the adapter's name.  A DenoiseLoop built before keeps the
+        operands it was built with: load and set adapters before the pipeline call."""
+        from .. import lora
+        return lora.load_lora_state_dict(self, state_dict, adapter_name=adapter_name, weight=weight)
+
+    def set_adapters(self, adapter_names, weights=None):
+        from .. import lora
+        lora.set_adapters(self, adapter_names, weights)
+
+    def get_active_adapters(self):
+        from .. import lora
+        return lora.get_active_adapters(self)
+
+    def delete_adapters(self, adapter_names):
+        from .. import lora
+        lora.delete_adapters(self, adapter_names)
+
+    def unload_lora(self):
+        """Every parameter back to its base tensor, bit for bit."""
+        from .. import lora
+        lora.unload(self)
+
     # ------------------------------------------------------------------ FreeU
     def enable_freeu(self, s1, s2, b1, b2):
         """diffusers' FreeUMixin.enable_freeu: s1 / b1 act in up_blocks[0], s2 / b2 in

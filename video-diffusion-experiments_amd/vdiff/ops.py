@@ -771,7 +771,36 @@ def euler_cfg_step(eps, ncfg, guidance, latents, coef, step_idx=None, x0_out=Non
           "vd_euler_cfg_step")
 
 
-SCHED_STEP = {"ddim": ddim_cfg_step, "euler": euler_cfg_step}
+STEP_LCM = 0x100  # VD_STEP_LCM, OR-ed into vd_ddim_cfg_step's ncfg
+LCM_ROW = 8       # floats per LCM coefficient row
+
+
+def lcm_buffer_numel(n_steps, latent_numel):
+    """Floats of the LCM coef buffer: n_steps rows of LCM_ROW, then n_steps noise slabs."""
+    return n_steps * (LCM_ROW + latent_numel)
+
+
+def lcm_cfg_step(eps, ncfg, guidance, latents, coef, step_idx=None, x0_out=None, next_in=None):
+    """CFG combine + LCMScheduler.step, fused (vd_ddim_cfg_step with VD_STEP_LCM).  `coef` is the
+    rows-plus-slabs buffer of include/vdiff.h: n rows of 8 floats, then n noise slabs of
+    latents.numel() floats; n is derived from its size.  x0_out receives diffusers' `denoised`."""
+    _dev(eps, latents, coef, step_idx, x0_out, next_in)
+    if latents.dtype != torch.float32 or not latents.is_contiguous():
+        raise ValueError("latents must be contiguous fp32")
+    if coef.dtype != torch.float32 or not coef.is_contiguous():
+        raise ValueError("lcm_cfg_step: coef must be a contiguous fp32 buffer")
+    per = LCM_ROW + latents.numel()
+    if coef.numel() == 0 or coef.numel() % per:
+        raise ValueError(f"lcm_cfg_step: coef holds {coef.numel()} floats, not a multiple of "
+                         f"{LCM_ROW} + {latents.numel()} (rows, then one noise slab per row)")
+    B, Cc, Fr, H, W = latents.shape
+    check(lib().vd_ddim_cfg_step(_p(eps), eps.stride(0), ncfg | STEP_LCM, guidance, _p(latents), B, Cc, Fr, H, W,
+                                 _p(coef), coef.numel() // per, _p(step_idx), _p(x0_out), _p(next_in),
+                                 next_in.shape[1] if next_in is not None else 0, _stream()),
+          "vd_ddim_cfg_step (VD_STEP_LCM)")
+
+
+SCHED_STEP = {"ddim": ddim_cfg_step, "euler": euler_cfg_step, "lcm": lcm_cfg_step}
 
 
 def step_advance(step_idx):

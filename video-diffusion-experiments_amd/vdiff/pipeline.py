@@ -44,6 +44,12 @@ FreeInit (diffusers' FreeInitMixin, `enable_free_init`) wraps the loop of both p
 is sampled num_iters times on ONE DenoiseLoop and one captured graph (`DenoiseLoop.reschedule`
 swaps in the shorter schedules of use_fast_sampling), and between two runs the latents are noised
 back with the initial noise and low-pass mixed with fresh noise by `ops.free_init_filter`.
+
+With a `vdiff.LCMScheduler` the step is stochastic: the pipelines draw the noise of every non-final
+step right after the initial latents (diffusers' draw order) and DenoiseLoop keeps it in device
+memory behind the coefficient rows, where the step kernel reads it by the device step counter —
+still one captured graph.  LoRAs (`load_lora_weights`, `set_adapters`, ... — vdiff.lora) are merged
+into the UNet's parameters before the call.
 """
 from __future__ import annotations
 
@@ -80,8 +86,13 @@ class DenoiseLoop:
 
     def __init__(self, unet: UNetMotionModel, scheduler, latents: torch.Tensor,
                  prompt_embeds: torch.Tensor, guidance_scale: float, timesteps=None,
-                 use_graph: bool = True, cfg_shard=None, ip_embeds=None):
-        """ip_embeds: the projected IP-Adapter image tokens [Bt, n, cross_attention_dim] (uncond
+                 use_graph: bool = True, cfg_shard=None, ip_embeds=None, step_noise=None):
+        """step_noise (an LCM scheduler only, where it is required): the noise of the stochastic
+        steps, [n_steps - 1 or n_steps, B, C, F, H, W] in step order (the last step adds none; a
+        row given for it is ignored).  It lives behind the coefficient rows in one device buffer
+        that the step kernel reads by the device step index, so the captured graph serves any
+        later reset(latents, step_noise=...).
+        ip_embeds: the projected IP-Adapter image tokens [Bt, n, cross_attention_dim] (uncond
         half first under CFG), or None.  They become n extra K/V rows per video in every spatial
         cross-attention (built once, in prime()'s eager step) and the attention launches take
         them as a second softmax segment; not supported together with cfg_shard.
@@ -104,11 +115,27 @@ class DenoiseLoop:
         self.n_steps = len(ts)
         self.capacity = len(ts)  # rows of the device tables: the longest schedule reschedule() takes
         self.ts = torch.as_tensor(ts).to(dev, torch.float32)
-        self.coef = scheduler.coefficient_table(torch.as_tensor(ts).cpu()).to(dev)
         # the scheduler's fused CFG+update kernel; Euler's also applies the next step's
         # scale_model_input, and the first input is packed with step 0's divisor
         self.kind = getattr(scheduler, "kind", "ddim")
         self.sched_step = ops.SCHED_STEP[self.kind]
+        rows = scheduler.coefficient_table(torch.as_tensor(ts).cpu())
+        if self.kind == "lcm":
+            # one buffer, built once at the loop's capacity: the rows, then one noise slab per row
+            if step_noise is None:
+                raise ValueError("an LCM DenoiseLoop needs step_noise: the noise of its stochastic steps, "
+                                 f"[{self.n_steps - 1} or {self.n_steps}, {', '.join(map(str, self.lat.shape))}]")
+            self.coef = torch.empty(ops.lcm_buffer_numel(self.capacity, self.lat.numel()), device=dev,
+                                    dtype=torch.float32)
+            self.coef_rows = self.coef[:ops.LCM_ROW * self.capacity].view(self.capacity, ops.LCM_ROW)
+            self.noise_slabs = self.coef[ops.LCM_ROW * self.capacity:].view(self.capacity, *self.lat.shape)
+            self.noise_slabs.zero_()  # the last step's slab is never read; keep it defined all the same
+            self.coef_rows.copy_(rows)
+            self._fill_step_noise(step_noise)
+        else:
+            if step_noise is not None:
+                raise ValueError(f"step_noise is for an LCM scheduler; this loop's is {self.kind!r}")
+            self.coef = self.coef_rows = rows.to(dev)
         self.in_div0 = 1.0
         if self.kind == "euler":
             self.in_div0 = scheduler.input_divisor(scheduler.index_for_timestep(float(torch.as_tensor(ts)[0])))
@@ -173,7 +200,22 @@ class DenoiseLoop:
                         next_in=self.x_in2)
         ops.step_advance(self.step_idx)
 
-    def reset(self, latents):
+    def _fill_step_noise(self, step_noise):
+        """Copy the schedule's step noise into the slabs behind the coefficient rows."""
+        want = tuple(self.lat.shape)
+        sn = torch.as_tensor(step_noise)
+        if sn.dim() != 6 or tuple(sn.shape[1:]) != want or sn.shape[0] not in (self.n_steps - 1, self.n_steps):
+            raise ValueError(f"step_noise of shape {tuple(sn.shape)}: expected [{self.n_steps - 1} or {self.n_steps}, "
+                             f"{', '.join(map(str, want))}] (one slab per stochastic step, in step order)")
+        self.noise_slabs[:sn.shape[0]].copy_(sn)
+
+    def reset(self, latents, step_noise=None):
+        """Back to step 0 with new latents; an LCM loop also takes the new run's step_noise (None
+        keeps the slabs it holds)."""
+        if step_noise is not None:
+            if self.kind != "lcm":
+                raise ValueError(f"step_noise is for an LCM scheduler; this loop's is {self.kind!r}")
+            self._fill_step_noise(step_noise)
         self.lat.copy_(latents)
         self.step_idx.zero_()
         self.issued = 0
@@ -190,7 +232,7 @@ class DenoiseLoop:
         if n < 1 or n > self.capacity:
             raise ValueError(f"reschedule: {n} timesteps, the loop's tables were built for 1..{self.capacity}")
         self.ts[:n].copy_(ts.to(self.ts.device, torch.float32))
-        self.coef[:n].copy_(self.scheduler.coefficient_table(ts.cpu()).to(self.coef.device))
+        self.coef_rows[:n].copy_(self.scheduler.coefficient_table(ts.cpu()).to(self.coef.device))
         if self.kind == "euler":
             self.in_div0 = self.scheduler.input_divisor(self.scheduler.index_for_timestep(float(ts[0])))
         self.n_steps = n
@@ -361,6 +403,42 @@ class AnimateDiffPipeline:
     def disable_freeu(self):
         self.unet.disable_freeu()
 
+    # ------------------------------------------------------------------ LoRA
+    def load_lora_weights(self, pretrained_model_name_or_path_or_dict, weight_name=None, subfolder=None,
+                          adapter_name=None, **unused):
+        """diffusers' load_lora_weights over LOCAL files (vdiff.lora): a state dict, a .safetensors /
+        .bin file, or a directory (+ subfolder, weight_name).  The LoRA is merged into the UNet's
+        parameters as a new active adapter of weight 1.0 (the adapters already active stay active)
+        and the operands are re-packed.  Like enable_freeu it acts on the next __call__, which
+        builds its DenoiseLoop — graph and cross-attention K/V cache included — from scratch."""
+        from . import lora
+        sd = lora.read_lora_file(pretrained_model_name_or_path_or_dict, weight_name=weight_name, subfolder=subfolder)
+        return self.unet.load_lora_state_dict(sd, adapter_name=adapter_name)
+
+    def set_adapters(self, adapter_names, adapter_weights=None):
+        """The active adapters and their weights (default 1.0 each); weight 0 is the base weight."""
+        self.unet.set_adapters(adapter_names, adapter_weights)
+
+    def get_active_adapters(self):
+        return self.unet.get_active_adapters()
+
+    def delete_adapters(self, adapter_names):
+        self.unet.delete_adapters(adapter_names)
+
+    def unload_lora_weights(self):
+        """Every UNet parameter back to its base tensor, bit for bit."""
+        self.unet.unload_lora()
+
+    def fuse_lora(self, lora_scale: float = 1.0, **unused):
+        """Accepted for diffusers' call sequence: the weights here are always merged, so this only
+        multiplies the active adapters' weights by lora_scale."""
+        from . import lora
+        lora.set_fuse_scale(self.unet, lora_scale)
+
+    def unfuse_lora(self, **unused):
+        from . import lora
+        lora.set_fuse_scale(self.unet, 1.0)
+
     # ------------------------------------------------------------------ FreeNoise
     FREE_NOISE_NOISE_TYPES = ("shuffle_context", "repeat_context", "random")
 
@@ -496,6 +574,32 @@ class AnimateDiffPipeline:
         self.scheduler.set_timesteps(self._free_init_steps(num_inference_steps, iteration))
         return latents, self.scheduler.timesteps
 
+    # ------------------------------------------------------------------ LCM step noise
+    @property
+    def _lcm(self) -> bool:
+        return getattr(self.scheduler, "kind", None) == "lcm"
+
+    def _refuse_sharded_lcm(self):
+        if self._lcm and self.dist is not None:
+            raise NotImplementedError("LCMScheduler with a frame-sharded pipeline (dist=) is not supported: the "
+                                      "per-step noise slabs are not sharded over the ranks' frames")
+
+    def _lcm_step_noise(self, latents, n_steps, generator, draw=True):
+        """The noise of an LCM schedule's n_steps - 1 stochastic steps, [n_steps - 1, *latents.shape]
+        (None for any other scheduler): one randn_tensor of the latents' shape per non-final step,
+        in step order, on the call's generator and in the dtype the initial noise is drawn in
+        (diffusers draws in model_output.dtype, the pipeline's torch_dtype).  That is the draw
+        order of diffusers' loop, where LCMScheduler.step is the only thing that draws.
+        draw=False gives zeros of that shape (a loop built before its noise is known)."""
+        if not self._lcm:
+            return None
+        shape = (max(n_steps - 1, 0),) + tuple(latents.shape)
+        if not draw or n_steps <= 1:
+            return torch.zeros(shape, device=latents.device, dtype=torch.float32)
+        dtype = self.torch_dtype or torch.float32
+        return torch.stack([randn_tensor(latents.shape, generator=generator, device=latents.device, dtype=dtype)
+                            for _ in range(n_steps - 1)]).to(torch.float32)
+
     def _free_init_sample(self, latents, num_inference_steps, generator, make_loop, schedule=lambda ts: ts):
         """The FreeInit iterations around one DenoiseLoop: make_loop(timesteps) builds it, once, for
         the longest schedule; schedule(timesteps) is what an iteration runs of its timesteps (the
@@ -511,7 +615,8 @@ class AnimateDiffPipeline:
                 if len(ts) != len(now) or not torch.equal(torch.as_tensor(ts).cpu(), torch.as_tensor(now).cpu()):
                     loop.reschedule(ts)
                     now = ts
-                loop.reset(latents)
+                # an LCM schedule: this iteration's step noise, drawn after _apply_free_init's draws
+                loop.reset(latents, step_noise=self._lcm_step_noise(latents, len(ts), generator))
                 latents = loop.run()
         finally:
             self._free_init_initial_noise = self._free_init_table = self._free_init_scratch = None
@@ -687,6 +792,7 @@ class AnimateDiffPipeline:
         if self.free_init_enabled and self.dist is not None:
             raise NotImplementedError("FreeInit with a frame-sharded pipeline (dist=) is not supported: the filter "
                                       "needs every frame of a video and the ranks would have to agree on z_rand")
+        self._refuse_sharded_lcm()
         if isinstance(prompt, dict) or isinstance(negative_prompt, dict):
             raise NotImplementedError("a {frame: text} prompt dict (FreeNoise prompt travel) is not supported: "
                                       "per-frame text embeddings need per-frame cross-attention K/V")
@@ -735,10 +841,13 @@ class AnimateDiffPipeline:
             out = self._free_init_sample(
                 latents, num_inference_steps, generator,
                 lambda ts: DenoiseLoop(self.unet, self.scheduler, latents, ehs, guidance_scale, timesteps=ts,
-                                       use_graph=use_graph, ip_embeds=ip_embeds))
+                                       use_graph=use_graph, ip_embeds=ip_embeds,
+                                       step_noise=self._lcm_step_noise(latents, len(ts), None, draw=False)))
         else:
+            # an LCM schedule's step noise: drawn right after the initial latents, in step order
+            step_noise = self._lcm_step_noise(latents, len(self.scheduler.timesteps), generator)
             loop = DenoiseLoop(self.unet, self.scheduler, local, ehs, guidance_scale,
-                               use_graph=use_graph, ip_embeds=ip_embeds).prime()
+                               use_graph=use_graph, ip_embeds=ip_embeds, step_noise=step_noise).prime()
             out = loop.run()
         if self.dist is not None:
             out = self.dist.all_gather_frames(out)
@@ -858,6 +967,7 @@ class AnimateDiffVideoToVideoPipeline(AnimateDiffPipeline):
             raise NotImplementedError(f"output_type {output_type!r}: use 'pil', 'pt', 'np' or 'latent'")
         if video is None and latents is None:
             raise ValueError("video or latents required")
+        self._refuse_sharded_lcm()
         if isinstance(prompt, dict) or isinstance(negative_prompt, dict):
             raise NotImplementedError("a {frame: text} prompt dict (FreeNoise prompt travel) is not supported: "
                                       "per-frame text embeddings need per-frame cross-attention K/V")
@@ -895,11 +1005,13 @@ class AnimateDiffVideoToVideoPipeline(AnimateDiffPipeline):
             out = self._free_init_sample(
                 latents, num_inference_steps, generator,
                 lambda t: DenoiseLoop(self.unet, self.scheduler, latents, ehs, guidance_scale, timesteps=t,
-                                      use_graph=use_graph, ip_embeds=ip_embeds),
+                                      use_graph=use_graph, ip_embeds=ip_embeds,
+                                      step_noise=self._lcm_step_noise(latents, len(t), None, draw=False)),
                 schedule=lambda t: self.get_timesteps(len(t), strength)[0])
         else:
+            step_noise = self._lcm_step_noise(latents, len(ts), generator)  # after prepare_latents' draws
             loop = DenoiseLoop(self.unet, self.scheduler, local, ehs, guidance_scale, timesteps=ts,
-                               use_graph=use_graph, ip_embeds=ip_embeds).prime()
+                               use_graph=use_graph, ip_embeds=ip_embeds, step_noise=step_noise).prime()
             out = loop.run()
         if self.dist is not None:
             out = self.dist.all_gather_frames(out)

@@ -107,6 +107,9 @@ def motion_unet_config(unet_cfg: dict, adapter_cfg: dict) -> dict:
         raise NotImplementedError("motion_layers_per_block != the UNet's layers_per_block")
     if adapter_cfg.get("motion_norm_num_groups", unet_cfg.get("norm_num_groups", 32)) != unet_cfg.get("norm_num_groups", 32):
         raise NotImplementedError("motion_norm_num_groups != norm_num_groups")
+    if unet_cfg.get("time_cond_proj_dim"):
+        raise NotImplementedError("time_cond_proj_dim (the guidance-scale embedding of a fully distilled LCM UNet) is "
+                                  "not built: load the base UNet and the LCM LoRA (pipe.load_lora_weights)")
     if adapter_cfg.get("conv_in_channels"):
         raise NotImplementedError("motion adapters with their own conv_in (PIA / SparseCtrl) are not on 05's path")
     cfg = get_config("full")
@@ -221,11 +224,12 @@ def load_tokenizer(tok_dir):
 def load_scheduler(sched_dir):
     """The pipeline's scheduler from scheduler_config.json.  SD-1.5 ships PNDMScheduler, which the
     reference immediately replaces (05:136-141 DDIM, 01/03 Euler) from `pipe.scheduler.config`;
-    DDIM / Euler configs build that class, anything else a DDIMScheduler holding the same config
+    DDIM / Euler / LCM configs build that class, anything else a DDIMScheduler holding the same config
     (its unknown keys are kept in `.config` so the reference's from_config(...) sees them)."""
-    from .sched import DDIMScheduler, EulerDiscreteScheduler
+    from .sched import DDIMScheduler, EulerDiscreteScheduler, LCMScheduler
     cfg = read_json(Path(sched_dir) / "scheduler_config.json")
-    cls = EulerDiscreteScheduler if cfg.get("_class_name") == "EulerDiscreteScheduler" else DDIMScheduler
+    cls = {"EulerDiscreteScheduler": EulerDiscreteScheduler, "LCMScheduler": LCMScheduler}.get(
+        cfg.get("_class_name"), DDIMScheduler)
     s = cls.from_config({k: v for k, v in cfg.items() if not k.startswith("_")})
     s.source_config = cfg
     return s

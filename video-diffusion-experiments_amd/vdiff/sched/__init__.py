@@ -1,2 +1,3 @@
 from .ddim import DDIMScheduler, DDIMSchedulerOutput  # noqa: F401
 from .euler import EulerDiscreteScheduler, EulerDiscreteSchedulerOutput  # noqa: F401
+from .lcm import LCMScheduler, LCMSchedulerOutput  # noqa: F401

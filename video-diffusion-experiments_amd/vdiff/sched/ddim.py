@@ -151,7 +151,8 @@ class DDIMScheduler:
         if self.num_inference_steps is None:
             raise ValueError("call set_timesteps() first")
         if eta != 0.0:
-            raise NotImplementedError("eta > 0 (the reference pipeline runs eta = 0)")
+            raise NotImplementedError("eta > 0 (the reference pipeline runs eta = 0; for a stochastic few-step "
+                                      "sampler see vdiff.LCMScheduler)")
         if not (model_output.is_cuda and sample.is_cuda):
             raise ValueError("DDIMScheduler.step runs the HIP kernel; tensors must be on the GPU")
         coef = self.coefficients(timestep).to(sample.device)
