@@ -626,6 +626,26 @@ int vd_block_transpose(const void* src, void* dst, int64_t nb, int64_t na, int64
  *   or not 16-byte aligned; out == x on p = 1, 5; out != x or ldo != ldx on p = 2..4; y NULL, not
  *   16-byte aligned or y_f32 != 1 on p = 1, 3, 5; y or y_f32 set on p = 2, 4; ldy != Wh on p = 3;
  *   a row stride shorter than its row (W for x / y / out rows, 2 * Wh for S) or an odd S stride.
+ *   Op 7, VD_ROWS_CTRL_ADD, is ControlNet's residual injection (diffusers' UNet forward adds the
+ *   scaled zero-conv outputs to the down-block skips and to the mid block's output), riding here
+ *   for the same reason as ops 2-6.  op = VD_ROWS_CTRL_ADD | VD_ROWS_CTRL_COL(i), i the table
+ *   column (the low byte is the op):
+ *     out[r][c] = bf16( fmaf(s, float(x[r][c]), float(out[r][c])) ),  r < rows, c < C,
+ *     s = tab[clamp(step, 0, y_period - 1) * ldy + i].
+ *   x = the control residual, bf16 rows of stride ldx; out = the skip, bf16 rows of stride ldo,
+ *   read and written in place (it may be a column or row slice of a wider buffer).  y = one fp32
+ *   control block in DEVICE memory, 16-byte aligned, y_f32 == 1: floats 0..3 are a header whose
+ *   word 0 is the int32 step index (the denoising loop's device step counter lives there, as the
+ *   LCM noise lives in coef: the kernel needs no extra pointer; words 1..3 are ignored), then
+ *   tab, y_period rows of ldy floats.  y_div is not read.  Step, scale and data are all read
+ *   inside the launch only, so a captured step replays over the whole schedule with the scale
+ *   changing between replays (control_guidance_start / end) and per residual (guess mode).
+ *   One fused multiply-add in fp32 and one rounding to bf16 per element, 16-byte chunks, no
+ *   atomics; s == 0 returns out as it was (a -0 may come back as +0).
+ *   VD_EINVAL, before any launch: x, y or out NULL or not 16-byte aligned; y_f32 != 1; ldy
+ *   outside 1..64; i >= ldy; any bit above the column byte; y_period < 1; C % 8; x == out; y not
+ *   inside a device allocation (hipPointerGetAttributes: every thread reads the step word through
+ *   it, and a plain op 7 with host operands stays refused as it was before the op existed).
  * vd_upsample_nearest2x: rows of n_img h x w images -> rows of their nearest x2 upsample
  *   (Upsample2D's F.interpolate(scale_factor=2.0, mode="nearest")). */
 enum {
@@ -635,10 +655,12 @@ enum {
   VD_ROWS_SCALE = 3,
   VD_ROWS_WIN_GATHER = 4,
   VD_ROWS_WIN_MERGE = 5,
-  VD_ROWS_SPECTRAL = 6
+  VD_ROWS_SPECTRAL = 6,
+  VD_ROWS_CTRL_ADD = 7
 };
 #define VD_ROWS_WIN_STRIDE(s) ((s) << 8)
 #define VD_ROWS_SPEC_PASS(p) ((p) << 8)
+#define VD_ROWS_CTRL_COL(i) ((i) << 8)
 #define VD_SPECTRAL_MAX 256
 int vd_rows_eltwise(int32_t op, const void* x, int64_t ldx, const void* y, int64_t ldy, int32_t y_f32,
                     int64_t y_div, int64_t y_period, int64_t rows, int64_t C, void* out, int64_t ldo,

@@ -27,7 +27,7 @@ __device__ __forceinline__ void load8_any(const void* p, int is_f32, float* f) {
 // op 0: out[r] = (x ? x[r] : 0) + y[(r / y_div) % y_period]     (y bf16 or fp32)
 // op 1: out[r] = silu(x[r])
 // op 3: out[r] = x[r] * *y                                        (y one fp32 on the device)
-// (op 2 is freeu_filter_kernel, ops 4 and 5 win_gather_kernel / win_merge_kernel below)
+// (op 2 is freeu_filter_kernel, ops 4 and 5 win_gather_kernel / win_merge_kernel, op 7 ctrl_add_kernel below)
 __global__ void rows_eltwise_kernel(int op, const bf16_t* x, int64_t ldx, const void* y, int64_t ldy, int y_f32,
                                     int64_t y_div, int64_t y_period, int64_t rows, int64_t C, bf16_t* out,
                                     int64_t ldo) {
@@ -301,12 +301,45 @@ __global__ __launch_bounds__(NT) void win_merge_kernel(const bf16_t* x, int64_t 
   }
 }
 
+// op 7, ControlNet's residual injection: out[r][c] += s * x[r][c], s one entry of the fp32 table
+// behind the control block's 4-float header, picked by the device step index in the header's
+// first word (clamped to the table) and the column the op word carries (include/vdiff.h).  Every
+// thread reads the same two words, so step, scale and data are all read inside the launch.
+__global__ __launch_bounds__(NT) void ctrl_add_kernel(const bf16_t* x, int64_t ldx, const float* blk, int ldy, int col,
+                                                      int period, int64_t rows, int64_t C, bf16_t* out, int64_t ldo) {
+  const int step = min(max(*(const int*)blk, 0), period - 1);
+  const float s = blk[4 + (int64_t)step * ldy + col];
+  const int64_t cpr = C / 8;
+  const int64_t total = rows * cpr;
+  for (int64_t i = (int64_t)blockIdx.x * NT + threadIdx.x; i < total; i += (int64_t)gridDim.x * NT) {
+    const int64_t r = i / cpr;
+    const int64_t c = (i - r * cpr) * 8;
+    float z[8], v[8];
+    unpack8(*(const uint4*)(x + r * ldx + c), z);
+    unpack8(*(const uint4*)(out + r * ldo + c), v);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = fmaf(s, z[j], v[j]);
+    *(uint4*)(out + r * ldo + c) = pack8(v);
+  }
+}
+
 unsigned grid_for(int64_t total) {
   const int64_t b = (total + NT - 1) / NT;
   return (unsigned)(b < 16384 ? (b > 0 ? b : 1) : 16384);
 }
 
 inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+// true for an address inside a device allocation (no launch, no synchronisation; a failed query
+// — a host address, no device — leaves no sticky error behind)
+inline bool on_device(const void* p) {
+  hipPointerAttribute_t a;
+  if (hipPointerGetAttributes(&a, p) != hipSuccess) {
+    (void)hipGetLastError();
+    return false;
+  }
+  return a.type == hipMemoryTypeDevice;
+}
 
 }  // namespace
 
@@ -322,6 +355,20 @@ extern "C" int vd_rows_eltwise(int32_t op, const void* x, int64_t ldx, const voi
   // op 6 carries its pass above the low byte (VD_ROWS_SPEC_PASS); none of the bf16 rules below apply
   if (op >= 0 && (op & 0xff) == VD_ROWS_SPECTRAL)
     return vdrows::spectral_launch(op >> 8, x, ldx, y, ldy, y_f32, y_div, y_period, rows, C, out, ldo, stream);
+  // op 7 carries its table column above the low byte (VD_ROWS_CTRL_COL); out is read and written
+  if (op >= 0 && (op & 0xff) == VD_ROWS_CTRL_ADD) {
+    const int32_t col = op >> 8;  // a bit above the column byte makes col > 255, past any ldy <= 64
+    VD_CHECK_ARG(x && y && out && al16(x) && al16(y) && al16(out) && x != out && y_f32 == 1);
+    VD_CHECK_ARG(ldy >= 1 && ldy <= 64 && col < ldy && y_period >= 1 && y_period <= 0x7fffffff);
+    VD_CHECK_ARG(rows > 0 && C > 0 && C % 8 == 0 && ldx % 8 == 0 && ldo % 8 == 0 && ldx >= C && ldo >= C);
+    // the control block must be DEVICE memory: every thread reads the step word through y before
+    // any bound is known, and before this op existed a plain op 7 was refused whatever its operands
+    VD_CHECK_ARG(on_device(y));
+    hipLaunchKernelGGL(ctrl_add_kernel, dim3(grid_for(rows * (C / 8))), dim3(NT), 0, (hipStream_t)stream,
+                       (const bf16_t*)x, ldx, (const float*)y, (int)ldy, (int)col, (int)y_period, rows, C,
+                       (bf16_t*)out, ldo);
+    return vd_launch_status();
+  }
   // ops 4 and 5 carry the window stride above the low byte (VD_ROWS_WIN_STRIDE); no other op does
   const int32_t win_s = op >> 8;
   const bool win = op >= 0 && ((op & 0xff) == VD_ROWS_WIN_GATHER || (op & 0xff) == VD_ROWS_WIN_MERGE);

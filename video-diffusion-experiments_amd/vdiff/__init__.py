@@ -6,6 +6,7 @@ experiments) over hand-written gfx950 HIP kernels in libvdiff_hip.so.
 """
 from .config import FULL, TINY, get_config  # noqa: F401
 from .models import UNetMotionModel, UNetMotionOutput  # noqa: F401
+from .models.controlnet import ControlNetModel, ControlNetOutput  # noqa: F401
 from .models.clip import CLIPTextModel, CLIPTextModelOutput  # noqa: F401
 from .models.clip import CLIPVisionModelWithProjection, ImageProjection  # noqa: F401
 from .image_processor import CLIPImageProcessor  # noqa: F401
@@ -13,8 +14,9 @@ from .models.dit import DiT3DModel, DiTDenoiseLoop, DiTOutput  # noqa: F401
 from .models.vae import (AutoencoderKL, AutoencoderKLOutput, DecoderOutput,  # noqa: F401
                          DiagonalGaussianDistribution)
 from .pretrained import MotionAdapter  # noqa: F401
-from .pipeline import (AnimateDiffPipeline, AnimateDiffPipelineOutput,  # noqa: F401
-                       AnimateDiffVideoToVideoPipeline, DenoiseLoop)
+from .pipeline import (AnimateDiffControlNetPipeline, AnimateDiffPipeline,  # noqa: F401
+                       AnimateDiffPipelineOutput, AnimateDiffVideoToVideoPipeline, ControlNetConditioning,
+                       DenoiseLoop)
 from .sched import (DDIMScheduler, DDIMSchedulerOutput, EulerDiscreteScheduler,  # noqa: F401
                     EulerDiscreteSchedulerOutput, LCMScheduler, LCMSchedulerOutput)
 from .tokenizer import CLIPTokenizer  # noqa: F401

@@ -24,7 +24,8 @@ from ..config import down_block_plan, get_config, up_block_plan
 from .blocks import (FREE_NOISE_WEIGHTING_SCHEMES, AnimateDiffTransformer3D, CrossAttnDownBlockMotion,
                      CrossAttnUpBlockMotion, Ctx, DownBlockMotion, ResnetBlock2D, UNetMidBlockCrossAttnMotion,
                      UpBlockMotion)
-from .layers import Act, Conv2d, GroupNorm, SiLU, TimestepEmbedding, Timesteps, bf, f32, fmap_rows, token_rows
+from .layers import (Act, Conv2d, GroupNorm, SiLU, TimestepEmbedding, Timesteps, add, bf, f32, fmap_rows, rows_fmap,
+                     token_rows)
 
 
 class FrozenDict(dict):
@@ -45,6 +46,19 @@ def fmap_rows_f32(x):
     return x.permute(0, 2, 3, 1).reshape(-1, x.shape[1])
 
 CIN_PAD = 8  # conv_in input channels padded 4 -> 8 (16-byte NHWC rows)
+
+
+class ControlResiduals:
+    """ControlNet residuals given to UNetMotionModel.forward, as bf16 NHWC rows: added as they
+    are (their scale is already in them) with ops.rows_add, in place."""
+
+    def __init__(self, down_rows, mid_rows):
+        self.down_rows, self.mid_rows = list(down_rows), mid_rows
+
+    def inject(self, skips, mid, ctx):
+        for s, r in zip(skips, self.down_rows):
+            ops.rows_add(s.t, r, out=s.t)
+        ops.rows_add(mid.t, self.mid_rows, out=mid.t)
 
 
 class UNetMotionModel(nn.Module):
@@ -243,8 +257,41 @@ class UNetMotionModel(nn.Module):
     def free_noise_enabled(self) -> bool:
         return any(m.free_noise_enabled for m in self.motion_modules_in_order())
 
-    def forward_rows(self, x_rows, h, w, ctx: Ctx):
-        """Packed NHWC input rows [batch*frames*h*w, 8] -> eps rows fp32 [..., out_channels]."""
+    def control_residual_shapes(self, n_img, h, w):
+        """(rows, channels) of every down-block skip, in order, then of the mid block's output:
+        what down_block_additional_residuals / mid_block_additional_residual must match."""
+        shapes = [(n_img * h * w, self.conv_in.out_channels)]
+        for blk in self.down_blocks:
+            c = blk.resnets[0].out_channels
+            shapes += [(n_img * h * w, c)] * len(blk.resnets)
+            if blk.downsamplers is not None:
+                h, w = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+                shapes.append((n_img * h * w, c))
+        return shapes + [(n_img * h * w, self.mid_block.resnets[-1].out_channels)]
+
+    def _control_residuals(self, down, mid, n_img, H, W):
+        """The two residual arguments of forward -> ControlResiduals, or None when neither is given."""
+        if down is None and mid is None:
+            return None
+        if down is None or mid is None:
+            raise ValueError("down_block_additional_residuals and mid_block_additional_residual go together "
+                             "(a ControlNet returns both)")
+        shapes = self.control_residual_shapes(n_img, H, W)
+        maps = list(down) + [mid]
+        if len(maps) != len(shapes):
+            raise ValueError(f"{len(maps) - 1} down-block residuals for this UNet's {len(shapes) - 1} skips")
+        for i, (m, (r, c)) in enumerate(zip(maps, shapes)):
+            if m.dim() != 4 or m.shape[0] != n_img or m.shape[1] != c or m.shape[0] * m.shape[2] * m.shape[3] != r:
+                raise ValueError(f"control residual {i} of shape {tuple(m.shape)}: expected ({n_img}, {c}, h, w) "
+                                 f"with {r // n_img} pixels")
+        rows = [fmap_rows(m.to(self.device)) for m in maps]
+        return ControlResiduals(rows[:-1], rows[-1])
+
+    def forward_rows(self, x_rows, h, w, ctx: Ctx, control=None):
+        """Packed NHWC input rows [batch*frames*h*w, 8] -> eps rows fp32 [..., out_channels].
+        control: an object whose inject(skips, mid, ctx) adds ControlNet residuals in place
+        (ControlResiduals, or the denoising loop's vdiff.pipeline.ControlState).  It runs after
+        the mid block: the last skip is also the mid block's input and must not change earlier."""
         g = self.config["norm_num_groups"]
         n_img = ctx.batch * ctx.frames
         blocks = list(self.down_blocks)
@@ -270,6 +317,8 @@ class UNetMotionModel(nn.Module):
             x, outs = blk.run(x, ctx, res0=res0) if i == 0 else blk.run(x, ctx)
             skips.extend(outs)
         x = self.mid_block.run(x, ctx)
+        if control is not None:
+            control.inject(skips, x, ctx)
         for blk in self.up_blocks:
             x = blk.run(x, ctx, skips)
         no = self.conv_norm_out
@@ -284,7 +333,7 @@ class UNetMotionModel(nn.Module):
             return True
         return any(m._forward_hooks or m._forward_pre_hooks for m in self.modules() if m is not self)
 
-    def forward_modules(self, sample, t, ehs):
+    def forward_modules(self, sample, t, ehs, control=None):
         """diffusers UNetMotionModel.forward module by module: every block
         and leaf through __call__ with diffusers-layout tensors, all on the HIP kernels — the
         path a forward-hook trace (experiments/03_trace_forward_pass.py:105-113) observes.
@@ -314,6 +363,9 @@ class UNetMotionModel(nn.Module):
                 h, res = blk(h, emb, encoder_hidden_states=ehs_rep, num_frames=Fr)
             skips = skips + res
         h = self.mid_block(h, emb, encoder_hidden_states=ehs_rep, num_frames=Fr)
+        if control is not None:  # diffusers: new skips = skip + residual, mid output + residual
+            skips = tuple(add(sk, rows_fmap(r, tuple(sk.shape))) for sk, r in zip(skips, control.down_rows))
+            h = add(h, rows_fmap(control.mid_rows, tuple(h.shape)))
         for blk in self.up_blocks:
             n = len(blk.resnets)
             res, skips = skips[-n:], skips[:-n]
@@ -330,9 +382,7 @@ class UNetMotionModel(nn.Module):
                 return_dict: bool = True, num_frames: Optional[int] = None):
         if not self._prepared:
             self.prepare()
-        for unsupported, name in ((timestep_cond, "timestep_cond"), (attention_mask, "attention_mask"),
-                                  (down_block_additional_residuals, "down_block_additional_residuals"),
-                                  (mid_block_additional_residual, "mid_block_additional_residual")):
+        for unsupported, name in ((timestep_cond, "timestep_cond"), (attention_mask, "attention_mask")):
             if unsupported is not None:
                 raise NotImplementedError(f"{name} is not used by the reference's pipeline")
         dev = self.device
@@ -343,13 +393,15 @@ class UNetMotionModel(nn.Module):
         t = t.to(torch.float32).expand(B).contiguous()
         ehs = encoder_hidden_states.to(device=dev, dtype=torch.bfloat16).contiguous()
         L = ehs.shape[1]
+        control = self._control_residuals(down_block_additional_residuals, mid_block_additional_residual,
+                                          B * Fr, H, W)
         if self.has_hooks():
-            out = self.forward_modules(sample.to(dev, torch.float32), t, ehs)
+            out = self.forward_modules(sample.to(dev, torch.float32), t, ehs, control=control)
         else:
             te = ops.timestep_embed(t, self.time_proj.num_channels)
             ctx = self.make_ctx(te, ehs.reshape(B * L, -1), B, Fr, L)
             x_rows = ops.pack_latents(sample.to(dev), dup=1, cpad=CIN_PAD)
-            eps_rows = self.forward_rows(x_rows, H, W, ctx)
+            eps_rows = self.forward_rows(x_rows, H, W, ctx, control=control)
             out = ops.unpack_nhwc(eps_rows, B, self.config["out_channels"], Fr, H, W)
         out = out.to(sample.dtype) if sample.dtype.is_floating_point else out
         return UNetMotionOutput(out) if return_dict else (out,)

@@ -932,6 +932,54 @@ def window_merge(xw, wt_dev, B, F, hw, L, s, out=None):
     return out
 
 
+ROWS_CTRL_ADD = 7            # VD_ROWS_CTRL_ADD
+ROWS_CTRL_COL_SHIFT = 8      # VD_ROWS_CTRL_COL(i) = i << 8
+CTRL_HEADER = 4              # floats before the table: word 0 the int32 step index, 1..3 unused
+CTRL_MAX_COLS = 64
+
+
+def ctrl_block(table, device=None):
+    """The control block of vd_rows_eltwise op 7 for a [steps][cols] scale table -> (block,
+    step_idx): one fp32 device buffer of CTRL_HEADER + steps * cols floats, the table behind the
+    header, and step_idx, an int32 view of the header's first word (zero).  The denoising loop
+    uses that view as its device step counter, so the op needs no pointer of its own for it."""
+    tab = torch.as_tensor(table, dtype=torch.float32)
+    if tab.dim() != 2 or tab.shape[0] < 1 or not 1 <= tab.shape[1] <= CTRL_MAX_COLS:
+        raise ValueError(f"ctrl_block: a [steps >= 1][1..{CTRL_MAX_COLS}] table, got {tuple(tab.shape)}")
+    device = tab.device if device is None else torch.device(device)
+    if device.type != "cuda":
+        raise ValueError("vdiff ops run on the GPU only (ctrl_block on a CPU device); no CPU fallback")
+    block = torch.zeros(CTRL_HEADER + tab.numel(), device=device, dtype=torch.float32)
+    block[CTRL_HEADER:].view(tab.shape).copy_(tab)
+    return block, block[:1].view(torch.int32)
+
+
+def ctrl_table(block, cols):
+    """The [steps][cols] table view of a ctrl_block buffer."""
+    return block[CTRL_HEADER:].view(-1, cols)
+
+
+def ctrl_add_(acc, res, block, col, cols=None):
+    """acc += s * res in place over bf16 rows (vd_rows_eltwise op 7), s = table[clamp(step)][col]
+    of `block` (ctrl_block), step the block's first word: all read on the device inside the
+    launch.  acc may be a row or column slice of a wider buffer.  cols: the table's row length
+    (default: the whole table is one row)."""
+    _dev(acc, res, block)
+    if block.dtype != torch.float32 or block.dim() != 1 or not block.is_contiguous() or block.numel() <= CTRL_HEADER:
+        raise ValueError("ctrl_add_: block must be a contiguous 1-D fp32 buffer from ctrl_block")
+    cols = block.numel() - CTRL_HEADER if cols is None else int(cols)
+    if cols < 1 or (block.numel() - CTRL_HEADER) % cols:
+        raise ValueError(f"ctrl_add_: the block's {block.numel() - CTRL_HEADER} table floats are not rows of {cols}")
+    if tuple(acc.shape) != tuple(res.shape):
+        raise ValueError(f"ctrl_add_: acc {tuple(acc.shape)} and res {tuple(res.shape)} differ")
+    if not 0 <= col < cols:
+        raise ValueError(f"ctrl_add_: column {col} outside the table's {cols}")
+    check(lib().vd_rows_eltwise(ROWS_CTRL_ADD | (col << ROWS_CTRL_COL_SHIFT), _p(res), _rows(res), _p(block), cols, 1,
+                                1, (block.numel() - CTRL_HEADER) // cols, acc.shape[0], acc.shape[1], _p(acc),
+                                _rows(acc), _stream()), "vd_rows_eltwise(ctrl_add)")
+    return acc
+
+
 ROWS_SPECTRAL = 6            # VD_ROWS_SPECTRAL
 ROWS_SPEC_PASS_SHIFT = 8     # VD_ROWS_SPEC_PASS(p) = p << 8, p in 1..5
 SPECTRAL_MAX = 256           # VD_SPECTRAL_MAX: the longest F, H or W

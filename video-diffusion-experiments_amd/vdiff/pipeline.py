@@ -50,6 +50,13 @@ step right after the initial latents (diffusers' draw order) and DenoiseLoop kee
 memory behind the coefficient rows, where the step kernel reads it by the device step counter —
 still one captured graph.  LoRAs (`load_lora_weights`, `set_adapters`, ... — vdiff.lora) are merged
 into the UNet's parameters before the call.
+
+AnimateDiffControlNetPipeline (diffusers' third AnimateDiff pipeline) conditions the video on
+per-frame control images: a `vdiff.ControlNetModel` runs on the step's input inside the same
+captured graph and its 13 residuals are added to the UNet's skips and mid-block output by
+`ops.ctrl_add_`, whose scale is read on the device from a [steps][13] table by the step index —
+control_guidance_start / end and guess mode change it between replays, not the graph.  The
+conditioning embedding depends on no timestep and is computed once per call.
 """
 from __future__ import annotations
 
@@ -61,12 +68,45 @@ import torch
 
 from . import ops
 from .models.clip import CLIPTextModel
+from .models.controlnet import ControlNetModel, control_scale_table
 from .models.unet_motion import CIN_PAD, UNetMotionModel
 from .models.vae import AutoencoderKL
 from .sched.ddim import DDIMScheduler
 from .weights import init_synthetic_
 
 AnimateDiffPipelineOutput = namedtuple("AnimateDiffPipelineOutput", ["frames"])
+
+
+class ControlNetConditioning:
+    """What DenoiseLoop(control=) takes: the ControlNet, the conditioning frames (B, 3, F, 8h, 8w)
+    fp32 in [0, 1] (one video is shared by the whole batch) and the arguments of diffusers' scale
+    rule (vdiff.models.controlnet.control_scale_table)."""
+
+    def __init__(self, controlnet, frames, scale=1.0, guess_mode=False, start=0.0, end=1.0):
+        if isinstance(controlnet, (list, tuple)):
+            raise NotImplementedError("a list of ControlNets (MultiControlNetModel) is not supported: pass one")
+        self.controlnet, self.frames = controlnet, frames
+        self.scale, self.guess_mode, self.start, self.end = scale, bool(guess_mode), start, end
+
+    def table(self, n_steps, n_res):
+        return control_scale_table(n_steps, n_res, self.scale, self.guess_mode, self.start, self.end)
+
+
+class ControlState:
+    """One step's ControlNet residuals and where their scales live: UNetMotionModel.forward_rows
+    calls inject() after the mid block.  cond_only (guess mode under CFG): the residuals are the
+    conditional half's and touch that half's rows alone."""
+
+    def __init__(self, residuals, block, cond_only):
+        self.residuals, self.block, self.cond_only = residuals, block, cond_only
+
+    def inject(self, skips, mid, ctx):
+        accs = [*skips, mid]
+        if len(accs) != len(self.residuals):
+            raise ValueError(f"{len(self.residuals)} ControlNet residuals for the UNet's {len(accs) - 1} skips + mid")
+        for i, (a, r) in enumerate(zip(accs, self.residuals)):
+            acc = a.t[a.t.shape[0] // 2:] if self.cond_only else a.t
+            ops.ctrl_add_(acc, r.t, self.block, i, cols=len(accs))
 
 
 class SyntheticTextEncoder:
@@ -86,7 +126,7 @@ class DenoiseLoop:
 
     def __init__(self, unet: UNetMotionModel, scheduler, latents: torch.Tensor,
                  prompt_embeds: torch.Tensor, guidance_scale: float, timesteps=None,
-                 use_graph: bool = True, cfg_shard=None, ip_embeds=None, step_noise=None):
+                 use_graph: bool = True, cfg_shard=None, ip_embeds=None, step_noise=None, control=None):
         """step_noise (an LCM scheduler only, where it is required): the noise of the stochastic
         steps, [n_steps - 1 or n_steps, B, C, F, H, W] in step order (the last step adds none; a
         row given for it is ignored).  It lives behind the coefficient rows in one device buffer
@@ -96,6 +136,11 @@ class DenoiseLoop:
         half first under CFG), or None.  They become n extra K/V rows per video in every spatial
         cross-attention (built once, in prime()'s eager step) and the attention launches take
         them as a second softmax segment; not supported together with cfg_shard.
+        control (ControlNetConditioning): the ControlNet runs on the step's input before the UNet
+        (on the conditional half alone in guess mode under CFG) with a Ctx and a cross-attention
+        K/V cache of its own, and its residuals are added after the UNet's mid block, scaled by the
+        [capacity][n] table behind the control block's header — whose first word is this loop's
+        device step counter.  Not supported under frame or CFG sharding.
         cfg_shard (vdiff.dist.CfgShard, CFG only): this rank runs the UNet on ONE half
         (cfg_shard.index: 0 uncond, 1 cond) and swaps eps rows with its pair before the
         fused CFG+scheduler update, which both ranks apply to their replicated latents
@@ -140,6 +185,22 @@ class DenoiseLoop:
         if self.kind == "euler":
             self.in_div0 = scheduler.input_divisor(scheduler.index_for_timestep(float(torch.as_tensor(ts)[0])))
         self.step_idx = torch.zeros(1, device=dev, dtype=torch.int32)
+        self.control = control
+        if control is not None:
+            if cfg_shard is not None or unet.dist is not None:
+                raise NotImplementedError("ControlNet under frame sharding (dist=) or CFG sharding (cfg_shard=) is "
+                                          "not supported: the residuals are not sharded over the ranks")
+            cn = control.controlnet
+            if not cn._prepared:
+                cn.prepare()
+            self.cn_res = cn.num_residuals
+            want = unet.control_residual_shapes(1, self.H, self.W)
+            if [c for _, c in want] != cn.residual_channels() or \
+                    cn.time_proj.num_channels != unet.time_proj.num_channels:
+                raise ValueError(f"the ControlNet's residual channels {cn.residual_channels()} do not fit the UNet's "
+                                 f"skips {[c for _, c in want]}")
+            # the step counter moves into the control block's header (ops.ctrl_block)
+            self.ctrl_block, self.step_idx = ops.ctrl_block(control.table(self.capacity, self.cn_res), dev)
         pe = prompt_embeds.to(dev, torch.bfloat16).contiguous()
         if pe.shape[0] != self.Bt:
             raise ValueError(f"prompt_embeds batch {pe.shape[0]} != {self.Bt} (uncond first when CFG)")
@@ -167,6 +228,21 @@ class DenoiseLoop:
         self.x_in2 = ops.pack_latents(self.lat, dup=self.ncfg, cpad=CIN_PAD, in_div=self.in_div0)
         self.x_in = self.x_in2[:self.Bu * self.F * self.H * self.W]
         self.kv_cache = {}
+        if control is not None:
+            fr = control.frames
+            if fr.dim() != 5 or fr.shape[0] not in (1, self.B) or fr.shape[2] != self.F or \
+                    tuple(fr.shape[3:]) != (8 * self.H, 8 * self.W):
+                raise ValueError(f"conditioning frames of shape {tuple(fr.shape)}: expected (1 or {self.B}, 3, {self.F}, "
+                                 f"{8 * self.H}, {8 * self.W})")
+            cond = control.controlnet.embed_condition(fr.expand(self.B, -1, -1, -1, -1))
+            # guess mode under CFG: the ControlNet sees the conditional half only
+            self.cn_cond_only = control.guess_mode and self.ncfg == 2
+            self.cn_batch = self.B if self.cn_cond_only else self.Bt
+            half = self.B * self.F * self.H * self.W
+            self.cn_cond_rows = cond if self.cn_batch == self.B else torch.cat([cond, cond])
+            self.cn_x_in = self.x_in[half:] if self.cn_cond_only else self.x_in
+            self.cn_ehs_rows = self.ehs_rows[self.B * self.L:] if self.cn_cond_only else self.ehs_rows
+            self.cn_kv_cache = {}
         # the FreeU scalars the step's launches (and the graph) read: kept alive for this loop's
         # life, whatever enable_freeu / disable_freeu does to the blocks afterwards
         self.freeu_operands = [b._freeu for b in unet.up_blocks]
@@ -193,7 +269,14 @@ class DenoiseLoop:
         te = ops.timestep_embed(self.ts, u.time_proj.num_channels, step_idx=self.step_idx, batch=self.Bu)
         ctx = u.make_ctx(te, self.ehs_rows, self.Bu, self.F, self.L, kv_cache=self.kv_cache, ip_rows=self.ip_rows)
         ctx.cfg_dup = self.cfg_dedup and self.Bu == self.Bt == 2 * self.B  # x_in = [lat; lat]
-        eps = u.forward_rows(self.x_in, self.H, self.W, ctx)
+        state = None
+        if self.control is not None:  # every row of te is the step's one timestep
+            cn = self.control.controlnet
+            cctx = cn.make_ctx(te[:self.cn_batch], self.cn_ehs_rows, self.cn_batch, self.F, self.L,
+                               kv_cache=self.cn_kv_cache)
+            res = cn.forward_rows(self.cn_x_in, self.cn_cond_rows, self.H, self.W, cctx)
+            state = ControlState(res, self.ctrl_block, self.cn_cond_only)
+        eps = u.forward_rows(self.x_in, self.H, self.W, ctx, control=state)
         if self.cfg_shard is not None:
             eps = self.cfg_shard.gather_eps(eps)
         self.sched_step(eps, self.ncfg, self.g, self.lat, self.coef, step_idx=self.step_idx,
@@ -235,6 +318,8 @@ class DenoiseLoop:
         self.coef_rows[:n].copy_(self.scheduler.coefficient_table(ts.cpu()).to(self.coef.device))
         if self.kind == "euler":
             self.in_div0 = self.scheduler.input_divisor(self.scheduler.index_for_timestep(float(ts[0])))
+        if self.control is not None:  # the new schedule's scales, by its own step count
+            ops.ctrl_table(self.ctrl_block, self.cn_res)[:n].copy_(self.control.table(n, self.cn_res))
         self.n_steps = n
         self.issued = n  # nothing may run before reset()
         return self
@@ -767,6 +852,10 @@ class AnimateDiffPipeline:
             return arr
         return [numpy_to_pil(a) for a in arr]
 
+    def _make_loop(self, *args, **kwargs):
+        """The call's DenoiseLoop (a subclass adds what its loop needs, e.g. control=)."""
+        return DenoiseLoop(*args, **kwargs)
+
     def prepare_latents(self, batch, num_frames, h, w, generator=None, latents=None):
         """diffusers AnimateDiffPipeline.prepare_latents -> fp32 on the GPU, x init_noise_sigma.
         The draw follows randn_tensor: on the generator's device (a CPU generator from 05:156's
@@ -840,14 +929,14 @@ class AnimateDiffPipeline:
         if self.free_init_enabled:
             out = self._free_init_sample(
                 latents, num_inference_steps, generator,
-                lambda ts: DenoiseLoop(self.unet, self.scheduler, latents, ehs, guidance_scale, timesteps=ts,
-                                       use_graph=use_graph, ip_embeds=ip_embeds,
-                                       step_noise=self._lcm_step_noise(latents, len(ts), None, draw=False)))
+                lambda ts: self._make_loop(self.unet, self.scheduler, latents, ehs, guidance_scale, timesteps=ts,
+                                           use_graph=use_graph, ip_embeds=ip_embeds,
+                                           step_noise=self._lcm_step_noise(latents, len(ts), None, draw=False)))
         else:
             # an LCM schedule's step noise: drawn right after the initial latents, in step order
             step_noise = self._lcm_step_noise(latents, len(self.scheduler.timesteps), generator)
-            loop = DenoiseLoop(self.unet, self.scheduler, local, ehs, guidance_scale,
-                               use_graph=use_graph, ip_embeds=ip_embeds, step_noise=step_noise).prime()
+            loop = self._make_loop(self.unet, self.scheduler, local, ehs, guidance_scale,
+                                   use_graph=use_graph, ip_embeds=ip_embeds, step_noise=step_noise).prime()
             out = loop.run()
         if self.dist is not None:
             out = self.dist.all_gather_frames(out)
@@ -861,6 +950,11 @@ def preprocess_video(video, height=None, width=None):
     PIL frames or a list of such lists; an ndarray (F, H, W, 3) or (B, F, H, W, 3) in [0, 1]; a
     tensor (F, 3, H, W) or (B, F, 3, H, W) in [0, 1].  height / width default to the video's own
     size.  PIL frames of another size are resized (LANCZOS); arrays and tensors are refused."""
+    return (2.0 * decode_video_frames(video, height, width) - 1.0).permute(0, 2, 1, 3, 4).contiguous()
+
+
+def decode_video_frames(video, height=None, width=None):
+    """preprocess_video's decoding, left in [0, 1]: -> (B, F, 3, H, W) fp32 on the CPU."""
     import numpy as np
     if isinstance(video, (list, tuple)) and len(video) > 0 and not torch.is_tensor(video[0]) \
             and not isinstance(video[0], np.ndarray):
@@ -893,7 +987,7 @@ def preprocess_video(video, height=None, width=None):
         raise ValueError(f"video is {H} x {W}, asked for {height} x {width}: only PIL frames are resized")
     if H % 8 or W % 8:
         raise ValueError(f"video height and width must be multiples of 8, got {H} x {W}")
-    return (2.0 * x - 1.0).permute(0, 2, 1, 3, 4).contiguous()
+    return x
 
 
 class AnimateDiffVideoToVideoPipeline(AnimateDiffPipeline):
@@ -1018,3 +1112,95 @@ class AnimateDiffVideoToVideoPipeline(AnimateDiffPipeline):
         if output_type != "latent":
             out = self.postprocess_video(self.decode_latents(out), output_type)
         return AnimateDiffPipelineOutput(frames=out) if return_dict else (out,)
+
+
+class AnimateDiffControlNetPipeline(AnimateDiffPipeline):
+    """diffusers AnimateDiffControlNetPipeline: `pipe(prompt=, conditioning_frames=, ...)` runs the
+    text-to-video pipeline's loop with a ControlNet on every step's input, inside the same
+    captured graph (DenoiseLoop(control=)).  IP-Adapter, FreeU, FreeNoise, LoRA and the LCM
+    scheduler combine with it as they do with the plain pipeline.  Refused: a list of ControlNets
+    (MultiControlNet), a frame-sharded pipeline (dist=), FreeInit.  Parity to diffusers is
+    unpinned, as the UNet's."""
+
+    def __init__(self, unet, controlnet, scheduler=None, text_encoder=None, vae=None, dist=None, tokenizer=None):
+        if isinstance(controlnet, (list, tuple)):
+            raise NotImplementedError("a list of ControlNets (MultiControlNetModel) is not supported: pass one")
+        if not isinstance(controlnet, ControlNetModel):
+            raise ValueError("AnimateDiffControlNetPipeline needs controlnet=vdiff.ControlNetModel(...)")
+        if dist is not None:
+            raise NotImplementedError("AnimateDiffControlNetPipeline with a frame-sharded pipeline (dist=) is not "
+                                      "supported: the ControlNet's residuals are not sharded over the ranks' frames")
+        super().__init__(unet, scheduler, text_encoder=text_encoder, vae=vae, dist=dist, tokenizer=tokenizer)
+        self.controlnet = controlnet
+        self._control = None  # the running call's ControlNetConditioning arguments
+
+    @classmethod
+    def from_config(cls, config="full", device="cuda", seed=0, scheduler=None, dist=None, vae="auto",
+                    controlnet_seed=1):
+        """Synthetic-weight pipeline: AnimateDiffPipeline.from_config's, plus a synthetic ControlNet
+        of the same config (its zero convs are NOT zero, or it would be invisible)."""
+        base = AnimateDiffPipeline.from_config(config, device=device, seed=seed, scheduler=scheduler, dist=None,
+                                               vae=vae)
+        cn = init_synthetic_(ControlNetModel(config), controlnet_seed).to(device=device, dtype=torch.bfloat16)
+        pipe = cls(base.unet, cn.prepare(), base.scheduler, vae=base.vae, dist=dist)
+        pipe.torch_dtype = base.torch_dtype
+        return pipe
+
+    @classmethod
+    def from_pretrained(cls, pretrained_model_name_or_path, controlnet=None, motion_adapter=None, **kwargs):
+        """AnimateDiffPipeline.from_pretrained's components plus controlnet=ControlNetModel.from_pretrained(...)."""
+        if controlnet is None:
+            raise ValueError("AnimateDiffControlNetPipeline needs controlnet=ControlNetModel.from_pretrained(...)")
+        if isinstance(controlnet, (list, tuple)):
+            raise NotImplementedError("a list of ControlNets (MultiControlNetModel) is not supported: pass one")
+        if kwargs.get("dist") is not None:
+            raise NotImplementedError("AnimateDiffControlNetPipeline with a frame-sharded pipeline (dist=) is not "
+                                      "supported")
+        base = AnimateDiffPipeline.from_pretrained(pretrained_model_name_or_path, motion_adapter=motion_adapter,
+                                                   **kwargs)
+        if controlnet.device.type == "cuda":
+            controlnet.prepare()
+        pipe = cls(base.unet, controlnet, base.scheduler, vae=base.vae, tokenizer=base.tokenizer,
+                   text_encoder=base.text_encoder if base.tokenizer is not None else None)
+        pipe.torch_dtype = base.torch_dtype
+        return pipe
+
+    def _make_loop(self, unet, scheduler, latents, *args, **kwargs):
+        c = self._control
+        control = ControlNetConditioning(self.controlnet, c["frames"], c["scale"], c["guess_mode"], c["start"],
+                                         c["end"])
+        return DenoiseLoop(unet, scheduler, latents, *args, control=control, **kwargs)
+
+    @torch.no_grad()
+    def __call__(self, prompt=None, num_frames=16, height=None, width=None, num_inference_steps=50,
+                 guidance_scale=7.5, *, conditioning_frames=None, controlnet_conditioning_scale=1.0,
+                 guess_mode=False, control_guidance_start=0.0, control_guidance_end=1.0, **kwargs):
+        if self.free_init_enabled:
+            raise NotImplementedError("FreeInit together with ControlNet is not supported: the guidance window is "
+                                      "laid out over one schedule, FreeInit runs several; disable_free_init()")
+        if self.dist is not None:
+            raise NotImplementedError("AnimateDiffControlNetPipeline with a frame-sharded pipeline (dist=) is not "
+                                      "supported")
+        if conditioning_frames is None:
+            raise ValueError("conditioning_frames required: one control image per frame")
+        for v in (controlnet_conditioning_scale, control_guidance_start, control_guidance_end):
+            if isinstance(v, (list, tuple)):
+                raise NotImplementedError("per-ControlNet lists of scales / guidance windows (MultiControlNet) are "
+                                          "not supported")
+        sample = self.unet.config["sample_size"]
+        height, width = height or sample * 8, width or sample * 8
+        frames = decode_video_frames(conditioning_frames, height, width).permute(0, 2, 1, 3, 4).contiguous()
+        if frames.shape[2] != num_frames:
+            raise ValueError(f"{frames.shape[2]} conditioning frames for num_frames={num_frames}")
+        if tuple(frames.shape[3:]) != (height, width):
+            raise ValueError(f"conditioning frames are {frames.shape[3]} x {frames.shape[4]}, the video "
+                             f"{height} x {width}")
+        control_scale_table(1, 1, controlnet_conditioning_scale, guess_mode, control_guidance_start,
+                            control_guidance_end)  # refuses a bad guidance window before any work
+        self._control = dict(frames=frames, scale=controlnet_conditioning_scale, guess_mode=guess_mode,
+                             start=control_guidance_start, end=control_guidance_end)
+        try:
+            return super().__call__(prompt=prompt, num_frames=num_frames, height=height, width=width,
+                                    num_inference_steps=num_inference_steps, guidance_scale=guidance_scale, **kwargs)
+        finally:
+            self._control = None
