@@ -509,9 +509,31 @@ int vd_lpips_pairs(const void* frames_u8, int64_t videos, int32_t frames, int32_
  *   Step st (= *step_idx clamped to the n_coef rows) reads row st and, only when that row's
  *   add_noise != 0, slab st: the last step's slab is sized but never read.  Step index, branch
  *   and noise are all read inside the launch, so a captured step replays over the whole schedule.
+ * VD_STEP_DPM OR-ed into vd_ddim_cfg_step's ncfg (0x400: 0x200 stays VD_EINVAL; together with
+ *   VD_STEP_LCM it is VD_EINVAL; vd_euler_cfg_step refuses it): the diffusers
+ *   DPMSolverMultistepScheduler.step update — "dpmsolver++" and "sde-dpmsolver++", midpoint,
+ *   solver order 1 or 2, epsilon prediction — in the same one-rounding-per-op fp32 arithmetic:
+ *     x0 = (x - sigma_s*eps) / alpha_s
+ *     x  <- c_x*x + c_m0*x0
+ *     second order:  x <- x + c_d1 * ((1/r0) * (x0 - m1))
+ *     SDE noise:     x <- x + c_noise * noise
+ *   coef is 16-byte aligned and holds n_coef rows of 8 floats
+ *     {alpha_s, sigma_s, c_x, c_m0, c_d1, 1/r0, c_noise, flags}, flags = 1.0 * second order +
+ *     2.0 * SDE noise; a slot its row does not use holds 0.0 and the whole table is finite.
+ *   diffusers writes the deterministic update with two subtractions; the host stores those two
+ *   coefficients (c_m0, c_d1) negated, so one add-only form serves both algorithm types
+ *   (a - c*b == a + (-c)*b bit for bit).  When any row has the SDE flag, n_coef slabs of
+ *   B*C*F*H*W floats follow from float offset 8*n_coef, as under VD_STEP_LCM; an SDE row reads
+ *   its slab on every step, the last included (its c_noise is 0 there, the slab must be finite).
+ *   x0_out is REQUIRED and is both input and output, the multistep history: on entry the previous
+ *   step's x0 (m1), read only when the row's second-order flag is set; on exit this step's x0.
+ *   Each thread reads m1[i] before it writes x0[i].  x0_out == NULL or x0_out == latents is
+ *   VD_EINVAL.  A first-order row (step 0 of any schedule) never reads it, so the history needs
+ *   no clearing between schedules.
  * vd_step_advance: ++*step_idx (one thread; the last node of a captured step).
  */
 enum { VD_STEP_LCM = 0x100 }; /* OR-ed into vd_ddim_cfg_step's ncfg, see above */
+enum { VD_STEP_DPM = 0x400 }; /* likewise; x0_out becomes the in/out history, see above */
 int vd_timestep_embed(const float* ts, int64_t n_ts, const int32_t* step_idx, int64_t B,
                       int32_t dim, void* out, vd_stream_t stream);
 int vd_pack_latents(const float* x, int64_t B, int64_t C, int64_t F, int64_t H, int64_t W,

@@ -10,7 +10,8 @@
 // Coefficients come from a device table indexed by a device step counter so a
 // captured hipGraph of one step can be replayed for every timestep.  With VD_STEP_LCM in ncfg
 // the same entry point launches the LCMScheduler update, whose per-step noise follows the
-// coefficient rows in the same device buffer (lcm_cfg_kernel).
+// coefficient rows in the same device buffer (lcm_cfg_kernel); with VD_STEP_DPM the
+// DPMSolverMultistepScheduler update, whose history travels in x0_out (dpm_cfg_kernel).
 #include "common.h"
 
 namespace {
@@ -214,6 +215,60 @@ __global__ void lcm_cfg_kernel(const float* eps, int64_t ld_eps, int ncfg, float
   }
 }
 
+// CFG combine + diffusers:DPMSolverMultistepScheduler.step (dpmsolver++ and sde-dpmsolver++,
+// midpoint, order 1 or 2, epsilon prediction), in diffusers' fp32 operation order
+// (vd_ddim_cfg_step with VD_STEP_DPM in ncfg):
+//   x0 = (x - sigma_s eps) / alpha_s;  x <- c_x x + c_m0 x0 [+ c_d1 (1/r0) (x0 - m1)] [+ c_noise noise]
+// coef holds n_coef rows of 8 floats {alpha_s, sigma_s, c_x, c_m0, c_d1, 1/r0, c_noise, flags}
+// (flags: 1.0 second order, 2.0 SDE noise, 3.0 both) and, when any row is an SDE row, n_coef noise
+// slabs of B*C*F*HW floats from float 8 * n_coef on.  The deterministic type's two subtracted
+// terms are stored negated, so both types share this add-only form (a - c b == a + (-c) b bit for
+// bit).  hist (x0_out) is in/out: the previous step's x0 on entry (m1, read only by a second-order
+// row), this step's on exit; each thread reads m1[i] before it writes x0[i].
+__global__ void dpm_cfg_kernel(const float* eps, int64_t ld_eps, int ncfg, float g, float* lat,
+                               int64_t B, int64_t C, int64_t F, int64_t HW, const float* coef,
+                               int64_t n_coef, const int32_t* step_idx, float* hist, bf16_t* next_in,
+                               int64_t cpad) {
+#pragma clang fp contract(off)  // one rounding per operation, as torch's separate fp32 ops
+  const int st = table_row(step_idx, n_coef);
+  const float* row = coef + 8 * (int64_t)st;
+  const float alpha_s = row[0], sigma_s = row[1], c_x = row[2], c_m0 = row[3];
+  const float c_d1 = row[4], inv_r0 = row[5], c_noise = row[6];
+  const int flags = (int)row[7];
+  const bool second = (flags & 1) != 0, sde = (flags & 2) != 0;
+  const int64_t total = B * C * F * HW;
+  const int64_t half_rows = B * F * HW;
+  const float* noise = coef + 8 * n_coef + (int64_t)st * total;
+  for (int64_t i = (int64_t)blockIdx.x * NT + threadIdx.x; i < total; i += (int64_t)gridDim.x * NT) {
+    const int64_t p = i % HW;
+    const int64_t f = (i / HW) % F;
+    const int64_t c = (i / (HW * F)) % C;
+    const int64_t b = i / (HW * F * C);
+    const int64_t r = (b * F + f) * HW + p;
+    float e = eps[r * ld_eps + c];
+    if (ncfg == 2) {
+      const float ec = eps[(r + half_rows) * ld_eps + c];
+      e = e + g * (ec - e);
+    }
+    const float x = lat[i];
+    const float x0 = div_rn(x - sigma_s * e, alpha_s);
+    float xn = c_x * x + c_m0 * x0;
+    if (second) {
+      const float d1 = inv_r0 * (x0 - hist[i]);
+      xn = xn + c_d1 * d1;
+    }
+    if (sde) xn = xn + c_noise * noise[i];
+    lat[i] = xn;
+    hist[i] = x0;
+    if (next_in) {
+      const bf16_t v = f2bf(xn);
+      next_in[r * cpad + c] = v;
+      if (ncfg == 2) next_in[(r + half_rows) * cpad + c] = v;
+      if (c == 0) zero_pad_cols(next_in, r, half_rows, ncfg, C, cpad);
+    }
+  }
+}
+
 __global__ void step_advance_kernel(int32_t* step_idx) { *step_idx += 1; }
 
 __global__ void block_transpose_kernel(const bf16_t* src, bf16_t* dst, int64_t nb, int64_t na,
@@ -270,14 +325,25 @@ extern "C" int vd_ddim_cfg_step(const float* eps, int64_t ld_eps, int32_t ncfg, 
                                 float* latents, int64_t B, int64_t C, int64_t F, int64_t H,
                                 int64_t W, const float* coef, int64_t n_coef, const int32_t* step_idx,
                                 float* x0_out, void* next_in, int64_t cpad, vd_stream_t stream) {
-  // VD_STEP_LCM rides on ncfg above its low byte; any other high bit is refused
-  const bool lcm = (ncfg & VD_STEP_LCM) != 0;
-  if (lcm) ncfg &= ~VD_STEP_LCM;
+  // VD_STEP_LCM / VD_STEP_DPM ride on ncfg above its low byte; both at once, or any other high
+  // bit, are refused
+  const bool lcm = (ncfg & VD_STEP_LCM) != 0, dpm = (ncfg & VD_STEP_DPM) != 0;
+  VD_CHECK_ARG(!(lcm && dpm));
+  ncfg &= ~(VD_STEP_LCM | VD_STEP_DPM);
   VD_CHECK_ARG(eps && latents && coef && n_coef > 0 && (ncfg == 1 || ncfg == 2) && ld_eps >= C);
   if (next_in) VD_CHECK_ARG(cpad >= C);
   if (lcm) {
     VD_CHECK_ARG(B > 0 && C > 0 && F > 0 && H > 0 && W > 0 && ((uintptr_t)coef & 15) == 0);
     hipLaunchKernelGGL(lcm_cfg_kernel, dim3(grid_for(B * C * F * H * W)), dim3(NT), 0,
+                       (hipStream_t)stream, eps, ld_eps, ncfg, guidance, latents, B, C, F, H * W,
+                       coef, n_coef, step_idx, x0_out, (bf16_t*)next_in, cpad);
+    return vd_launch_status();
+  }
+  if (dpm) {
+    // x0_out is the history: required, in/out, and not the latents themselves
+    VD_CHECK_ARG(B > 0 && C > 0 && F > 0 && H > 0 && W > 0 && ((uintptr_t)coef & 15) == 0);
+    VD_CHECK_ARG(x0_out && x0_out != latents);
+    hipLaunchKernelGGL(dpm_cfg_kernel, dim3(grid_for(B * C * F * H * W)), dim3(NT), 0,
                        (hipStream_t)stream, eps, ld_eps, ncfg, guidance, latents, B, C, F, H * W,
                        coef, n_coef, step_idx, x0_out, (bf16_t*)next_in, cpad);
     return vd_launch_status();

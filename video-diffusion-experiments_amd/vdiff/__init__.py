@@ -17,7 +17,8 @@ from .pretrained import MotionAdapter  # noqa: F401
 from .pipeline import (AnimateDiffControlNetPipeline, AnimateDiffPipeline,  # noqa: F401
                        AnimateDiffPipelineOutput, AnimateDiffVideoToVideoPipeline, ControlNetConditioning,
                        DenoiseLoop)
-from .sched import (DDIMScheduler, DDIMSchedulerOutput, EulerDiscreteScheduler,  # noqa: F401
-                    EulerDiscreteSchedulerOutput, LCMScheduler, LCMSchedulerOutput)
+from .sched import (DDIMScheduler, DDIMSchedulerOutput, DPMSolverMultistepScheduler,  # noqa: F401
+                    DPMSolverMultistepSchedulerOutput, EulerDiscreteScheduler, EulerDiscreteSchedulerOutput,
+                    LCMScheduler, LCMSchedulerOutput)
 from .tokenizer import CLIPTokenizer  # noqa: F401
 from .weights import init_synthetic_, load_diffusers_state_dict  # noqa: F401

@@ -800,7 +800,50 @@ def lcm_cfg_step(eps, ncfg, guidance, latents, coef, step_idx=None, x0_out=None,
           "vd_ddim_cfg_step (VD_STEP_LCM)")
 
 
-SCHED_STEP = {"ddim": ddim_cfg_step, "euler": euler_cfg_step, "lcm": lcm_cfg_step}
+STEP_DPM = 0x400  # VD_STEP_DPM, OR-ed into vd_ddim_cfg_step's ncfg
+DPM_ROW = 8       # floats per DPM-Solver coefficient row
+
+
+def dpm_buffer_numel(n_steps, latent_numel, sde):
+    """Floats of the DPM coef buffer: n_steps rows of DPM_ROW and, for the SDE type, n_steps noise
+    slabs behind them (LCM's layout); the deterministic type has rows alone."""
+    return n_steps * (DPM_ROW + (latent_numel if sde else 0))
+
+
+def dpm_cfg_step(eps, ncfg, guidance, latents, coef, step_idx=None, x0_out=None, next_in=None):
+    """CFG combine + DPMSolverMultistepScheduler.step, fused (vd_ddim_cfg_step with VD_STEP_DPM).
+    `coef` is the buffer of include/vdiff.h.  Its shape tells which of the two layouts it has:
+    [n, 8] is a table of rows alone (the deterministic type: no row of it may carry the SDE
+    flag, whose slab the kernel would look for behind the rows); a flat buffer holds n rows and
+    then n noise slabs of latents.numel() floats, n derived from its size.
+    x0_out is required: the history, the previous step's x0 on entry and this step's on exit."""
+    _dev(eps, latents, coef, step_idx, x0_out, next_in)
+    if latents.dtype != torch.float32 or not latents.is_contiguous():
+        raise ValueError("latents must be contiguous fp32")
+    if coef.dtype != torch.float32 or not coef.is_contiguous():
+        raise ValueError("dpm_cfg_step: coef must be a contiguous fp32 buffer")
+    if x0_out is None or x0_out.dtype != torch.float32 or not x0_out.is_contiguous() \
+            or x0_out.numel() != latents.numel():
+        raise ValueError("dpm_cfg_step: x0_out (the multistep history, in and out) must be a contiguous fp32 "
+                         "tensor of the latents' size")
+    if coef.dim() == 2:
+        if coef.shape[1] != DPM_ROW or coef.shape[0] == 0:
+            raise ValueError(f"dpm_cfg_step: a 2-D coef is [n, {DPM_ROW}] rows, got {tuple(coef.shape)}")
+        n = coef.shape[0]
+    else:
+        per = DPM_ROW + latents.numel()
+        if coef.dim() != 1 or coef.numel() == 0 or coef.numel() % per:
+            raise ValueError(f"dpm_cfg_step: a flat coef holds rows and slabs; {coef.numel()} floats are not a "
+                             f"multiple of {DPM_ROW} + {latents.numel()} (a table of rows alone is [n, {DPM_ROW}])")
+        n = coef.numel() // per
+    B, Cc, Fr, H, W = latents.shape
+    check(lib().vd_ddim_cfg_step(_p(eps), eps.stride(0), ncfg | STEP_DPM, guidance, _p(latents), B, Cc, Fr, H, W,
+                                 _p(coef), n, _p(step_idx), _p(x0_out), _p(next_in),
+                                 next_in.shape[1] if next_in is not None else 0, _stream()),
+          "vd_ddim_cfg_step (VD_STEP_DPM)")
+
+
+SCHED_STEP = {"ddim": ddim_cfg_step, "euler": euler_cfg_step, "lcm": lcm_cfg_step, "dpm": dpm_cfg_step}
 
 
 def step_advance(step_idx):

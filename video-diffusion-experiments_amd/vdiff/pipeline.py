@@ -51,6 +51,11 @@ memory behind the coefficient rows, where the step kernel reads it by the device
 still one captured graph.  LoRAs (`load_lora_weights`, `set_adapters`, ... — vdiff.lora) are merged
 into the UNet's parameters before the call.
 
+With a `vdiff.DPMSolverMultistepScheduler` (DPM-Solver++ 2M, usually 20-25 steps) the step is
+multistep: DenoiseLoop holds the previous step's x0 prediction in `x0_hist`, which the step kernel
+reads and overwrites in place, so the state is carried from one graph replay to the next without
+host work.  Its SDE type draws one fp32 noise slab per step, kept behind the rows as LCM's are.
+
 AnimateDiffControlNetPipeline (diffusers' third AnimateDiff pipeline) conditions the video on
 per-frame control images: a `vdiff.ControlNetModel` runs on the step's input inside the same
 captured graph and its 13 residuals are added to the UNet's skips and mid-block output by
@@ -127,11 +132,12 @@ class DenoiseLoop:
     def __init__(self, unet: UNetMotionModel, scheduler, latents: torch.Tensor,
                  prompt_embeds: torch.Tensor, guidance_scale: float, timesteps=None,
                  use_graph: bool = True, cfg_shard=None, ip_embeds=None, step_noise=None, control=None):
-        """step_noise (an LCM scheduler only, where it is required): the noise of the stochastic
-        steps, [n_steps - 1 or n_steps, B, C, F, H, W] in step order (the last step adds none; a
-        row given for it is ignored).  It lives behind the coefficient rows in one device buffer
-        that the step kernel reads by the device step index, so the captured graph serves any
-        later reset(latents, step_noise=...).
+        """step_noise (a stochastic scheduler only, where it is required): the noise of the
+        stochastic steps in step order.  LCM: [n_steps - 1 or n_steps, B, C, F, H, W] (the last
+        step adds none; a row given for it is ignored).  The SDE type of
+        DPMSolverMultistepScheduler: [n_steps, B, C, F, H, W], every step adds noise.  It lives
+        behind the coefficient rows in one device buffer that the step kernel reads by the device
+        step index, so the captured graph serves any later reset(latents, step_noise=...).
         ip_embeds: the projected IP-Adapter image tokens [Bt, n, cross_attention_dim] (uncond
         half first under CFG), or None.  They become n extra K/V rows per video in every spatial
         cross-attention (built once, in prime()'s eager step) and the attention launches take
@@ -165,6 +171,8 @@ class DenoiseLoop:
         self.kind = getattr(scheduler, "kind", "ddim")
         self.sched_step = ops.SCHED_STEP[self.kind]
         rows = scheduler.coefficient_table(torch.as_tensor(ts).cpu())
+        # the SDE type of DPMSolverMultistepScheduler adds noise on EVERY step, LCM on all but the last
+        self.dpm_sde = self.kind == "dpm" and scheduler.sde
         if self.kind == "lcm":
             # one buffer, built once at the loop's capacity: the rows, then one noise slab per row
             if step_noise is None:
@@ -177,10 +185,29 @@ class DenoiseLoop:
             self.noise_slabs.zero_()  # the last step's slab is never read; keep it defined all the same
             self.coef_rows.copy_(rows)
             self._fill_step_noise(step_noise)
+        elif self.dpm_sde:
+            # LCM's layout; every slab is read, the last step's too (times a zero coefficient)
+            if step_noise is None:
+                raise ValueError("a DenoiseLoop of the SDE type of DPMSolverMultistepScheduler needs step_noise: one "
+                                 f"slab per step, [{self.n_steps}, {', '.join(map(str, self.lat.shape))}]")
+            self.coef = torch.empty(ops.dpm_buffer_numel(self.capacity, self.lat.numel(), True), device=dev,
+                                    dtype=torch.float32)
+            self.coef_rows = self.coef[:ops.DPM_ROW * self.capacity].view(self.capacity, ops.DPM_ROW)
+            self.noise_slabs = self.coef[ops.DPM_ROW * self.capacity:].view(self.capacity, *self.lat.shape)
+            self.noise_slabs.zero_()
+            self.coef_rows.copy_(rows)
+            self._fill_step_noise(step_noise)
         else:
             if step_noise is not None:
-                raise ValueError(f"step_noise is for an LCM scheduler; this loop's is {self.kind!r}")
+                raise ValueError("step_noise is for an LCM scheduler or the SDE type of DPMSolverMultistepScheduler; "
+                                 f"this loop's is {self.kind!r}")
             self.coef = self.coef_rows = rows.to(dev)
+        # a multistep scheduler's state between two replays: the previous step's x0 prediction, which
+        # the step kernel reads and overwrites in place.  Step 0 of a schedule never reads it.
+        self.step_kwargs = {}
+        if self.kind == "dpm":
+            self.x0_hist = torch.empty_like(self.lat)
+            self.step_kwargs = dict(x0_out=self.x0_hist)
         self.in_div0 = 1.0
         if self.kind == "euler":
             self.in_div0 = scheduler.input_divisor(scheduler.index_for_timestep(float(torch.as_tensor(ts)[0])))
@@ -280,24 +307,27 @@ class DenoiseLoop:
         if self.cfg_shard is not None:
             eps = self.cfg_shard.gather_eps(eps)
         self.sched_step(eps, self.ncfg, self.g, self.lat, self.coef, step_idx=self.step_idx,
-                        next_in=self.x_in2)
+                        next_in=self.x_in2, **self.step_kwargs)
         ops.step_advance(self.step_idx)
 
     def _fill_step_noise(self, step_noise):
         """Copy the schedule's step noise into the slabs behind the coefficient rows."""
         want = tuple(self.lat.shape)
         sn = torch.as_tensor(step_noise)
-        if sn.dim() != 6 or tuple(sn.shape[1:]) != want or sn.shape[0] not in (self.n_steps - 1, self.n_steps):
-            raise ValueError(f"step_noise of shape {tuple(sn.shape)}: expected [{self.n_steps - 1} or {self.n_steps}, "
+        counts = (self.n_steps,) if self.dpm_sde else (self.n_steps - 1, self.n_steps)
+        if sn.dim() != 6 or tuple(sn.shape[1:]) != want or sn.shape[0] not in counts:
+            raise ValueError(f"step_noise of shape {tuple(sn.shape)}: expected [{' or '.join(map(str, counts))}, "
                              f"{', '.join(map(str, want))}] (one slab per stochastic step, in step order)")
         self.noise_slabs[:sn.shape[0]].copy_(sn)
 
     def reset(self, latents, step_noise=None):
-        """Back to step 0 with new latents; an LCM loop also takes the new run's step_noise (None
-        keeps the slabs it holds)."""
+        """Back to step 0 with new latents; a loop with step noise (LCM, the SDE type of
+        DPMSolverMultistepScheduler) also takes the new run's step_noise (None keeps the slabs it
+        holds).  A multistep loop's history needs no clearing: step 0 never reads it."""
         if step_noise is not None:
-            if self.kind != "lcm":
-                raise ValueError(f"step_noise is for an LCM scheduler; this loop's is {self.kind!r}")
+            if self.kind != "lcm" and not self.dpm_sde:
+                raise ValueError("step_noise is for an LCM scheduler or the SDE type of DPMSolverMultistepScheduler; "
+                                 f"this loop's is {self.kind!r}")
             self._fill_step_noise(step_noise)
         self.lat.copy_(latents)
         self.step_idx.zero_()
@@ -659,23 +689,48 @@ class AnimateDiffPipeline:
         self.scheduler.set_timesteps(self._free_init_steps(num_inference_steps, iteration))
         return latents, self.scheduler.timesteps
 
-    # ------------------------------------------------------------------ LCM step noise
+    # ------------------------------------------------------------------ the scheduler's step noise
     @property
     def _lcm(self) -> bool:
         return getattr(self.scheduler, "kind", None) == "lcm"
 
-    def _refuse_sharded_lcm(self):
+    @property
+    def _dpm(self) -> bool:
+        return getattr(self.scheduler, "kind", None) == "dpm"
+
+    @property
+    def _dpm_sde(self) -> bool:
+        return self._dpm and self.scheduler.sde
+
+    def _refuse_scheduler_combinations(self):
+        """What a stochastic or multistep scheduler does not combine with."""
         if self._lcm and self.dist is not None:
             raise NotImplementedError("LCMScheduler with a frame-sharded pipeline (dist=) is not supported: the "
                                       "per-step noise slabs are not sharded over the ranks' frames")
+        if self._dpm_sde and self.dist is not None:
+            raise NotImplementedError("DPMSolverMultistepScheduler's algorithm_type 'sde-dpmsolver++' with a "
+                                      "frame-sharded pipeline (dist=) is not supported: the per-step noise slabs are "
+                                      "not sharded over the ranks' frames ('dpmsolver++' is)")
+        if self._dpm and self.free_init_enabled:
+            raise NotImplementedError("FreeInit with DPMSolverMultistepScheduler is not supported: diffusers' "
+                                      "add_noise at a timestep outside the schedule falls back to the last sigma; "
+                                      "disable_free_init(), or use DDIMScheduler")
 
-    def _lcm_step_noise(self, latents, n_steps, generator, draw=True):
-        """The noise of an LCM schedule's n_steps - 1 stochastic steps, [n_steps - 1, *latents.shape]
-        (None for any other scheduler): one randn_tensor of the latents' shape per non-final step,
-        in step order, on the call's generator and in the dtype the initial noise is drawn in
-        (diffusers draws in model_output.dtype, the pipeline's torch_dtype).  That is the draw
-        order of diffusers' loop, where LCMScheduler.step is the only thing that draws.
-        draw=False gives zeros of that shape (a loop built before its noise is known)."""
+    def _step_noise(self, latents, n_steps, generator, draw=True):
+        """The scheduler's step noise, None for a deterministic one.
+        LCM: its n_steps - 1 stochastic steps', [n_steps - 1, *latents.shape]: one randn_tensor of
+        the latents' shape per non-final step, in step order, on the call's generator and in the
+        dtype the initial noise is drawn in (diffusers draws in model_output.dtype, the pipeline's
+        torch_dtype).  The SDE type of DPMSolverMultistepScheduler: [n_steps, *latents.shape], one
+        fp32 draw per step, the last included (diffusers draws there too, and multiplies by 0).
+        Either way that is the draw order of diffusers' loop, where scheduler.step is the only
+        thing that draws.  draw=False gives zeros of that shape (a loop built before its noise is
+        known)."""
+        if self._dpm_sde:
+            if not draw:
+                return torch.zeros((n_steps,) + tuple(latents.shape), device=latents.device, dtype=torch.float32)
+            return torch.stack([randn_tensor(latents.shape, generator=generator, device=latents.device,
+                                             dtype=torch.float32) for _ in range(n_steps)])
         if not self._lcm:
             return None
         shape = (max(n_steps - 1, 0),) + tuple(latents.shape)
@@ -701,7 +756,7 @@ class AnimateDiffPipeline:
                     loop.reschedule(ts)
                     now = ts
                 # an LCM schedule: this iteration's step noise, drawn after _apply_free_init's draws
-                loop.reset(latents, step_noise=self._lcm_step_noise(latents, len(ts), generator))
+                loop.reset(latents, step_noise=self._step_noise(latents, len(ts), generator))
                 latents = loop.run()
         finally:
             self._free_init_initial_noise = self._free_init_table = self._free_init_scratch = None
@@ -881,7 +936,7 @@ class AnimateDiffPipeline:
         if self.free_init_enabled and self.dist is not None:
             raise NotImplementedError("FreeInit with a frame-sharded pipeline (dist=) is not supported: the filter "
                                       "needs every frame of a video and the ranks would have to agree on z_rand")
-        self._refuse_sharded_lcm()
+        self._refuse_scheduler_combinations()
         if isinstance(prompt, dict) or isinstance(negative_prompt, dict):
             raise NotImplementedError("a {frame: text} prompt dict (FreeNoise prompt travel) is not supported: "
                                       "per-frame text embeddings need per-frame cross-attention K/V")
@@ -931,10 +986,10 @@ class AnimateDiffPipeline:
                 latents, num_inference_steps, generator,
                 lambda ts: self._make_loop(self.unet, self.scheduler, latents, ehs, guidance_scale, timesteps=ts,
                                            use_graph=use_graph, ip_embeds=ip_embeds,
-                                           step_noise=self._lcm_step_noise(latents, len(ts), None, draw=False)))
+                                           step_noise=self._step_noise(latents, len(ts), None, draw=False)))
         else:
             # an LCM schedule's step noise: drawn right after the initial latents, in step order
-            step_noise = self._lcm_step_noise(latents, len(self.scheduler.timesteps), generator)
+            step_noise = self._step_noise(latents, len(self.scheduler.timesteps), generator)
             loop = self._make_loop(self.unet, self.scheduler, local, ehs, guidance_scale,
                                    use_graph=use_graph, ip_embeds=ip_embeds, step_noise=step_noise).prime()
             out = loop.run()
@@ -1061,7 +1116,7 @@ class AnimateDiffVideoToVideoPipeline(AnimateDiffPipeline):
             raise NotImplementedError(f"output_type {output_type!r}: use 'pil', 'pt', 'np' or 'latent'")
         if video is None and latents is None:
             raise ValueError("video or latents required")
-        self._refuse_sharded_lcm()
+        self._refuse_scheduler_combinations()
         if isinstance(prompt, dict) or isinstance(negative_prompt, dict):
             raise NotImplementedError("a {frame: text} prompt dict (FreeNoise prompt travel) is not supported: "
                                       "per-frame text embeddings need per-frame cross-attention K/V")
@@ -1100,10 +1155,10 @@ class AnimateDiffVideoToVideoPipeline(AnimateDiffPipeline):
                 latents, num_inference_steps, generator,
                 lambda t: DenoiseLoop(self.unet, self.scheduler, latents, ehs, guidance_scale, timesteps=t,
                                       use_graph=use_graph, ip_embeds=ip_embeds,
-                                      step_noise=self._lcm_step_noise(latents, len(t), None, draw=False)),
+                                      step_noise=self._step_noise(latents, len(t), None, draw=False)),
                 schedule=lambda t: self.get_timesteps(len(t), strength)[0])
         else:
-            step_noise = self._lcm_step_noise(latents, len(ts), generator)  # after prepare_latents' draws
+            step_noise = self._step_noise(latents, len(ts), generator)  # after prepare_latents' draws
             loop = DenoiseLoop(self.unet, self.scheduler, local, ehs, guidance_scale, timesteps=ts,
                                use_graph=use_graph, ip_embeds=ip_embeds, step_noise=step_noise).prime()
             out = loop.run()
