@@ -530,10 +530,31 @@ int vd_lpips_pairs(const void* frames_u8, int64_t videos, int32_t frames, int32_
  *   Each thread reads m1[i] before it writes x0[i].  x0_out == NULL or x0_out == latents is
  *   VD_EINVAL.  A first-order row (step 0 of any schedule) never reads it, so the history needs
  *   no clearing between schedules.
+ * VD_STEP_PAG OR-ed into ncfg (0x800) of vd_ddim_cfg_step — alone, or with VD_STEP_LCM or
+ *   VD_STEP_DPM — or of vd_euler_cfg_step: perturbed-attention guidance (diffusers' PAGMixin).  The
+ *   low byte is then 2 or 3 (anything else is VD_EINVAL; without the flag 3 stays VD_EINVAL):
+ *     3: eps rows [uncond; cond; perturbed], each of B*F*H*W rows,
+ *          e = (e_u + g*(e_c - e_u)) + s*(e_c - e_p)
+ *     2: eps rows [cond; perturbed] (no CFG; guidance is ignored),
+ *          e = e_c + s*(e_c - e_p)
+ *   in the same one-rounding-per-op fp32 arithmetic, in exactly this order; the scheduler update
+ *   that follows is unchanged.  s is the per-step PAG scale (it changes with the step under
+ *   adaptive scaling) and travels in coef, which under the flag must be 16-byte aligned and holds
+ *     n_coef fp32 PAG scales, padded with (-n_coef mod 4) floats to a multiple of 4 (the padding
+ *       is never read), then
+ *     the scheduler's unchanged layout, from float offset 4*ceil(n_coef/4): n_coef rows of 4
+ *       (DDIM, Euler) or 8 (LCM, DPM) floats and, where that scheduler has them, its n_coef noise
+ *       slabs behind the rows.  The padding keeps the 16-byte alignment LCM and DPM ask for.
+ *   s = pag[st], st the same clamped device step index that picks the coefficient row, read inside
+ *   the launch.  The scales must be finite and >= 0; this library cannot read device memory, so
+ *   the caller checks that (vdiff.ops.pag_coef does).  next_in receives one copy of the packed
+ *   input per branch (2 or 3), the padding columns of every copy zero.  x0_out, DPM's history and
+ *   LCM's `denoised` keep their meaning.
  * vd_step_advance: ++*step_idx (one thread; the last node of a captured step).
  */
 enum { VD_STEP_LCM = 0x100 }; /* OR-ed into vd_ddim_cfg_step's ncfg, see above */
 enum { VD_STEP_DPM = 0x400 }; /* likewise; x0_out becomes the in/out history, see above */
+enum { VD_STEP_PAG = 0x800 }; /* into either step's ncfg: a third branch, scales in front of coef */
 int vd_timestep_embed(const float* ts, int64_t n_ts, const int32_t* step_idx, int64_t B,
                       int32_t dim, void* out, vd_stream_t stream);
 int vd_pack_latents(const float* x, int64_t B, int64_t C, int64_t F, int64_t H, int64_t W,

@@ -78,15 +78,36 @@ __global__ void unpack_kernel(const void* src, int src_f32, int64_t ld, int64_t 
   }
 }
 
-// next_in is the whole packed UNet input, as vd_pack_latents writes it: the channel padding
-// [C, cpad) of a row is zero.  The thread of the row's channel 0 writes it, so a next_in that
-// was never packed before (a fresh allocation) is fully defined after the step.
-__device__ __forceinline__ void zero_pad_cols(bf16_t* next_in, int64_t r, int64_t half_rows, int ncfg, int64_t C,
-                                              int64_t cpad) {
-  for (int64_t c = C; c < cpad; ++c) {
-    next_in[r * cpad + c] = 0;
-    if (ncfg == 2) next_in[(r + half_rows) * cpad + c] = 0;
+// next_in is the whole packed UNet input, as vd_pack_latents writes it: `copies` copies of the
+// batch (one per guidance branch), the channel padding [C, cpad) of every row zero.  The thread
+// of the row's channel 0 writes the padding, so a next_in that was never packed before (a fresh
+// allocation) is fully defined after the step.
+__device__ __forceinline__ void write_next_in(bf16_t* next_in, bf16_t v, int64_t r, int64_t c,
+                                              int64_t half_rows, int copies, int64_t C, int64_t cpad) {
+  for (int k = 0; k < copies; ++k) {
+    bf16_t* row = next_in + (r + k * half_rows) * cpad;
+    row[c] = v;
+    if (c == 0)
+      for (int64_t cc = C; cc < cpad; ++cc) row[cc] = 0;
   }
+}
+
+// The guided eps of one element, shared by the four step kernels.  eps holds ncfg branches of
+// half_rows rows each.  Without PAG (pag == nullptr): ncfg 1 is the row itself, ncfg 2 is
+// [uncond; cond] and e = e_u + g (e_c - e_u).  With PAG (s = pag[st], read by the caller):
+// ncfg 3 is [uncond; cond; perturbed], e = (e_u + g (e_c - e_u)) + s (e_c - e_p); ncfg 2 is
+// [cond; perturbed], e = e_c + s (e_c - e_p).  fp32, one rounding per operation.
+__device__ __forceinline__ float guided_eps(const float* eps, int64_t ld_eps, int64_t r, int64_t c,
+                                            int64_t half_rows, int ncfg, float g, bool pag, float s) {
+#pragma clang fp contract(off)
+  const float e0 = eps[r * ld_eps + c];
+  if (ncfg == 1) return e0;
+  const float e1 = eps[(r + half_rows) * ld_eps + c];
+  if (!pag) return e0 + g * (e1 - e0);
+  if (ncfg == 2) return e0 + s * (e0 - e1);
+  const float ep = eps[(r + 2 * half_rows) * ld_eps + c];
+  const float e = e0 + g * (e1 - e0);
+  return e + s * (e1 - ep);
 }
 
 // fp32 in diffusers' operation order with one rounding per operation (no contraction,
@@ -94,9 +115,10 @@ __device__ __forceinline__ void zero_pad_cols(bf16_t* next_in, int64_t r, int64_
 __global__ void ddim_cfg_kernel(const float* eps, int64_t ld_eps, int ncfg, float g, float* lat,
                                 int64_t B, int64_t C, int64_t F, int64_t HW, const float* coef,
                                 int64_t n_coef, const int32_t* step_idx, float* x0_out, bf16_t* next_in,
-                                int64_t cpad) {
+                                int64_t cpad, const float* pag) {
 #pragma clang fp contract(off)
   const int st = table_row(step_idx, n_coef);
+  const float pag_s = pag ? pag[st] : 0.f;
   const float sat = coef[4 * st + 0], s1at = coef[4 * st + 1];
   const float sap = coef[4 * st + 2], s1ap = coef[4 * st + 3];
   const int64_t total = B * C * F * HW;
@@ -107,22 +129,13 @@ __global__ void ddim_cfg_kernel(const float* eps, int64_t ld_eps, int ncfg, floa
     const int64_t c = (i / (HW * F)) % C;
     const int64_t b = i / (HW * F * C);
     const int64_t r = (b * F + f) * HW + p;
-    float e = eps[r * ld_eps + c];
-    if (ncfg == 2) {
-      const float ec = eps[(r + half_rows) * ld_eps + c];
-      e = e + g * (ec - e);
-    }
+    const float e = guided_eps(eps, ld_eps, r, c, half_rows, ncfg, g, pag != nullptr, pag_s);
     const float x = lat[i];
     const float x0 = div_rn(x - s1at * e, sat);
     const float xn = sap * x0 + s1ap * e;
     lat[i] = xn;
     if (x0_out) x0_out[i] = x0;
-    if (next_in) {
-      const bf16_t v = f2bf(xn);
-      next_in[r * cpad + c] = v;
-      if (ncfg == 2) next_in[(r + half_rows) * cpad + c] = v;
-      if (c == 0) zero_pad_cols(next_in, r, half_rows, ncfg, C, cpad);
-    }
+    if (next_in) write_next_in(next_in, f2bf(xn), r, c, half_rows, ncfg, C, cpad);
   }
 }
 
@@ -134,9 +147,10 @@ __global__ void ddim_cfg_kernel(const float* eps, int64_t ld_eps, int ncfg, floa
 __global__ void euler_cfg_kernel(const float* eps, int64_t ld_eps, int ncfg, float g, float* lat,
                                  int64_t B, int64_t C, int64_t F, int64_t HW, const float* coef,
                                  int64_t n_coef, const int32_t* step_idx, float* x0_out, bf16_t* next_in,
-                                 int64_t cpad) {
+                                 int64_t cpad, const float* pag) {
 #pragma clang fp contract(off)  // one rounding per operation, as torch's separate fp32 ops
   const int st = table_row(step_idx, n_coef);
+  const float pag_s = pag ? pag[st] : 0.f;
   const float sig = coef[4 * st + 0], sig_n = coef[4 * st + 1], in_div = coef[4 * st + 2];
   const float dt = sig_n - sig;
   const int64_t total = B * C * F * HW;
@@ -147,23 +161,14 @@ __global__ void euler_cfg_kernel(const float* eps, int64_t ld_eps, int ncfg, flo
     const int64_t c = (i / (HW * F)) % C;
     const int64_t b = i / (HW * F * C);
     const int64_t r = (b * F + f) * HW + p;
-    float e = eps[r * ld_eps + c];
-    if (ncfg == 2) {
-      const float ec = eps[(r + half_rows) * ld_eps + c];
-      e = e + g * (ec - e);
-    }
+    const float e = guided_eps(eps, ld_eps, r, c, half_rows, ncfg, g, pag != nullptr, pag_s);
     const float x = lat[i];
     const float x0 = x - sig * e;
     const float d = div_rn(x - x0, sig);
     const float xn = x + d * dt;
     lat[i] = xn;
     if (x0_out) x0_out[i] = x0;
-    if (next_in) {
-      const bf16_t v = f2bf(div_rn(xn, in_div));
-      next_in[r * cpad + c] = v;
-      if (ncfg == 2) next_in[(r + half_rows) * cpad + c] = v;
-      if (c == 0) zero_pad_cols(next_in, r, half_rows, ncfg, C, cpad);
-    }
+    if (next_in) write_next_in(next_in, f2bf(div_rn(xn, in_div)), r, c, half_rows, ncfg, C, cpad);
   }
 }
 
@@ -178,9 +183,10 @@ __global__ void euler_cfg_kernel(const float* eps, int64_t ld_eps, int ncfg, flo
 __global__ void lcm_cfg_kernel(const float* eps, int64_t ld_eps, int ncfg, float g, float* lat,
                                int64_t B, int64_t C, int64_t F, int64_t HW, const float* coef,
                                int64_t n_coef, const int32_t* step_idx, float* x0_out, bf16_t* next_in,
-                               int64_t cpad) {
+                               int64_t cpad, const float* pag) {
 #pragma clang fp contract(off)  // one rounding per operation, as torch's separate fp32 ops
   const int st = table_row(step_idx, n_coef);
+  const float pag_s = pag ? pag[st] : 0.f;
   const float* row = coef + 8 * (int64_t)st;
   const float sat = row[0], s1at = row[1], sap = row[2], s1ap = row[3];
   const float c_skip = row[4], c_out = row[5];
@@ -194,11 +200,7 @@ __global__ void lcm_cfg_kernel(const float* eps, int64_t ld_eps, int ncfg, float
     const int64_t c = (i / (HW * F)) % C;
     const int64_t b = i / (HW * F * C);
     const int64_t r = (b * F + f) * HW + p;
-    float e = eps[r * ld_eps + c];
-    if (ncfg == 2) {
-      const float ec = eps[(r + half_rows) * ld_eps + c];
-      e = e + g * (ec - e);
-    }
+    const float e = guided_eps(eps, ld_eps, r, c, half_rows, ncfg, g, pag != nullptr, pag_s);
     const float x = lat[i];
     const float x0 = div_rn(x - s1at * e, sat);
     const float den = c_out * x0 + c_skip * x;
@@ -206,12 +208,7 @@ __global__ void lcm_cfg_kernel(const float* eps, int64_t ld_eps, int ncfg, float
     if (add_noise) xn = sap * den + s1ap * noise[i];
     lat[i] = xn;
     if (x0_out) x0_out[i] = den;
-    if (next_in) {
-      const bf16_t v = f2bf(xn);
-      next_in[r * cpad + c] = v;
-      if (ncfg == 2) next_in[(r + half_rows) * cpad + c] = v;
-      if (c == 0) zero_pad_cols(next_in, r, half_rows, ncfg, C, cpad);
-    }
+    if (next_in) write_next_in(next_in, f2bf(xn), r, c, half_rows, ncfg, C, cpad);
   }
 }
 
@@ -228,9 +225,10 @@ __global__ void lcm_cfg_kernel(const float* eps, int64_t ld_eps, int ncfg, float
 __global__ void dpm_cfg_kernel(const float* eps, int64_t ld_eps, int ncfg, float g, float* lat,
                                int64_t B, int64_t C, int64_t F, int64_t HW, const float* coef,
                                int64_t n_coef, const int32_t* step_idx, float* hist, bf16_t* next_in,
-                               int64_t cpad) {
+                               int64_t cpad, const float* pag) {
 #pragma clang fp contract(off)  // one rounding per operation, as torch's separate fp32 ops
   const int st = table_row(step_idx, n_coef);
+  const float pag_s = pag ? pag[st] : 0.f;
   const float* row = coef + 8 * (int64_t)st;
   const float alpha_s = row[0], sigma_s = row[1], c_x = row[2], c_m0 = row[3];
   const float c_d1 = row[4], inv_r0 = row[5], c_noise = row[6];
@@ -245,11 +243,7 @@ __global__ void dpm_cfg_kernel(const float* eps, int64_t ld_eps, int ncfg, float
     const int64_t c = (i / (HW * F)) % C;
     const int64_t b = i / (HW * F * C);
     const int64_t r = (b * F + f) * HW + p;
-    float e = eps[r * ld_eps + c];
-    if (ncfg == 2) {
-      const float ec = eps[(r + half_rows) * ld_eps + c];
-      e = e + g * (ec - e);
-    }
+    const float e = guided_eps(eps, ld_eps, r, c, half_rows, ncfg, g, pag != nullptr, pag_s);
     const float x = lat[i];
     const float x0 = div_rn(x - sigma_s * e, alpha_s);
     float xn = c_x * x + c_m0 * x0;
@@ -260,12 +254,7 @@ __global__ void dpm_cfg_kernel(const float* eps, int64_t ld_eps, int ncfg, float
     if (sde) xn = xn + c_noise * noise[i];
     lat[i] = xn;
     hist[i] = x0;
-    if (next_in) {
-      const bf16_t v = f2bf(xn);
-      next_in[r * cpad + c] = v;
-      if (ncfg == 2) next_in[(r + half_rows) * cpad + c] = v;
-      if (c == 0) zero_pad_cols(next_in, r, half_rows, ncfg, C, cpad);
-    }
+    if (next_in) write_next_in(next_in, f2bf(xn), r, c, half_rows, ncfg, C, cpad);
   }
 }
 
@@ -321,22 +310,38 @@ extern "C" int vd_unpack_nhwc(const void* src, int32_t src_f32, int64_t ld, int6
   return vd_launch_status();
 }
 
+// VD_STEP_PAG: the low byte is 2 or 3 and coef starts with the n_coef PAG scales, padded to a
+// multiple of 4 floats; the scheduler's own layout follows.  Splits coef into the two, or refuses.
+static int split_pag_coef(int32_t& ncfg, const float*& coef, int64_t n_coef, const float*& pag) {
+  pag = nullptr;
+  const bool on = (ncfg & VD_STEP_PAG) != 0;
+  ncfg &= ~VD_STEP_PAG;
+  if (!on) return VD_OK;
+  VD_CHECK_ARG(coef && n_coef > 0 && (ncfg == 2 || ncfg == 3) && ((uintptr_t)coef & 15) == 0);
+  pag = coef;
+  coef += (n_coef + 3) / 4 * 4;
+  return VD_OK;
+}
+
 extern "C" int vd_ddim_cfg_step(const float* eps, int64_t ld_eps, int32_t ncfg, float guidance,
                                 float* latents, int64_t B, int64_t C, int64_t F, int64_t H,
                                 int64_t W, const float* coef, int64_t n_coef, const int32_t* step_idx,
                                 float* x0_out, void* next_in, int64_t cpad, vd_stream_t stream) {
   // VD_STEP_LCM / VD_STEP_DPM ride on ncfg above its low byte; both at once, or any other high
-  // bit, are refused
+  // bit but VD_STEP_PAG, are refused
   const bool lcm = (ncfg & VD_STEP_LCM) != 0, dpm = (ncfg & VD_STEP_DPM) != 0;
   VD_CHECK_ARG(!(lcm && dpm));
   ncfg &= ~(VD_STEP_LCM | VD_STEP_DPM);
-  VD_CHECK_ARG(eps && latents && coef && n_coef > 0 && (ncfg == 1 || ncfg == 2) && ld_eps >= C);
+  const float* pag;
+  if (const int rc = split_pag_coef(ncfg, coef, n_coef, pag)) return rc;
+  VD_CHECK_ARG(eps && latents && coef && n_coef > 0 && ld_eps >= C);
+  VD_CHECK_ARG(pag ? (ncfg == 2 || ncfg == 3) : (ncfg == 1 || ncfg == 2));
   if (next_in) VD_CHECK_ARG(cpad >= C);
   if (lcm) {
     VD_CHECK_ARG(B > 0 && C > 0 && F > 0 && H > 0 && W > 0 && ((uintptr_t)coef & 15) == 0);
     hipLaunchKernelGGL(lcm_cfg_kernel, dim3(grid_for(B * C * F * H * W)), dim3(NT), 0,
                        (hipStream_t)stream, eps, ld_eps, ncfg, guidance, latents, B, C, F, H * W,
-                       coef, n_coef, step_idx, x0_out, (bf16_t*)next_in, cpad);
+                       coef, n_coef, step_idx, x0_out, (bf16_t*)next_in, cpad, pag);
     return vd_launch_status();
   }
   if (dpm) {
@@ -345,12 +350,12 @@ extern "C" int vd_ddim_cfg_step(const float* eps, int64_t ld_eps, int32_t ncfg, 
     VD_CHECK_ARG(x0_out && x0_out != latents);
     hipLaunchKernelGGL(dpm_cfg_kernel, dim3(grid_for(B * C * F * H * W)), dim3(NT), 0,
                        (hipStream_t)stream, eps, ld_eps, ncfg, guidance, latents, B, C, F, H * W,
-                       coef, n_coef, step_idx, x0_out, (bf16_t*)next_in, cpad);
+                       coef, n_coef, step_idx, x0_out, (bf16_t*)next_in, cpad, pag);
     return vd_launch_status();
   }
   hipLaunchKernelGGL(ddim_cfg_kernel, dim3(grid_for(B * C * F * H * W)), dim3(NT), 0,
                      (hipStream_t)stream, eps, ld_eps, ncfg, guidance, latents, B, C, F, H * W,
-                     coef, n_coef, step_idx, x0_out, (bf16_t*)next_in, cpad);
+                     coef, n_coef, step_idx, x0_out, (bf16_t*)next_in, cpad, pag);
   return vd_launch_status();
 }
 
@@ -358,11 +363,15 @@ extern "C" int vd_euler_cfg_step(const float* eps, int64_t ld_eps, int32_t ncfg,
                                  float* latents, int64_t B, int64_t C, int64_t F, int64_t H,
                                  int64_t W, const float* coef, int64_t n_coef, const int32_t* step_idx,
                                  float* x0_out, void* next_in, int64_t cpad, vd_stream_t stream) {
-  VD_CHECK_ARG(eps && latents && coef && n_coef > 0 && (ncfg == 1 || ncfg == 2) && ld_eps >= C);
+  // VD_STEP_PAG is the one flag Euler takes; VD_STEP_LCM / VD_STEP_DPM fail the low-byte check
+  const float* pag;
+  if (const int rc = split_pag_coef(ncfg, coef, n_coef, pag)) return rc;
+  VD_CHECK_ARG(eps && latents && coef && n_coef > 0 && ld_eps >= C);
+  VD_CHECK_ARG(pag ? (ncfg == 2 || ncfg == 3) : (ncfg == 1 || ncfg == 2));
   if (next_in) VD_CHECK_ARG(cpad >= C);
   hipLaunchKernelGGL(euler_cfg_kernel, dim3(grid_for(B * C * F * H * W)), dim3(NT), 0,
                      (hipStream_t)stream, eps, ld_eps, ncfg, guidance, latents, B, C, F, H * W,
-                     coef, n_coef, step_idx, x0_out, (bf16_t*)next_in, cpad);
+                     coef, n_coef, step_idx, x0_out, (bf16_t*)next_in, cpad, pag);
   return vd_launch_status();
 }
 

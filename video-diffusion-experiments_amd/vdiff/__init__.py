@@ -14,9 +14,9 @@ from .models.dit import DiT3DModel, DiTDenoiseLoop, DiTOutput  # noqa: F401
 from .models.vae import (AutoencoderKL, AutoencoderKLOutput, DecoderOutput,  # noqa: F401
                          DiagonalGaussianDistribution)
 from .pretrained import MotionAdapter  # noqa: F401
-from .pipeline import (AnimateDiffControlNetPipeline, AnimateDiffPipeline,  # noqa: F401
+from .pipeline import (AnimateDiffControlNetPipeline, AnimateDiffPAGPipeline, AnimateDiffPipeline,  # noqa: F401
                        AnimateDiffPipelineOutput, AnimateDiffVideoToVideoPipeline, ControlNetConditioning,
-                       DenoiseLoop)
+                       DenoiseLoop, PerturbedAttentionGuidance)
 from .sched import (DDIMScheduler, DDIMSchedulerOutput, DPMSolverMultistepScheduler,  # noqa: F401
                     DPMSolverMultistepSchedulerOutput, EulerDiscreteScheduler, EulerDiscreteSchedulerOutput,
                     LCMScheduler, LCMSchedulerOutput)

@@ -48,6 +48,9 @@ class Ctx:
         # the two CFG halves of the input are the same latents (DenoiseLoop): everything before
         # the first cross-attention — conv_in and down_blocks[0].resnets[0] — runs on one half
         self.cfg_dup = False
+        # perturbed-attention guidance: the LAST pag_batch videos of the batch are the perturbed
+        # branch; a self-attention with .pag set runs them with an identity attention map
+        self.pag_batch = 0
 
 
 def concat_channels(a, b):
@@ -204,6 +207,37 @@ class BasicTransformerBlock(nn.Module):
         f3 = self.fold(3, h.shape[0]) if n is None else None
         return self.ff.forward_rows(h if n is None else n, h, fold=f3)
 
+    # perturbed-attention guidance (diffusers' PAGIdentitySelfAttnProcessor2_0 / PAGCFGIdentity...):
+    # rows are batch-major, so the perturbed branch is the row range [Mk, M).  Its attention map is
+    # the identity: the attention output is the V projection of the normalised rows — no Q, no K,
+    # no attention launch.  The rows before Mk run the plain path at the smaller batch.
+    @staticmethod
+    def _pag_kept(attn, M, batch, pag_batch):
+        """Rows of the unperturbed branches (M when this attention is not perturbed)."""
+        if not pag_batch or not attn.pag:
+            return M
+        if not 0 < pag_batch < batch or M % batch:
+            raise ValueError(f"PAG: {pag_batch} perturbed videos in a batch of {batch} ({M} rows)")
+        return M - M // batch * pag_batch
+
+    def _pag_spatial(self, h, n, Mk, n_img_k, hw):
+        """attn1 of a spatial block with the rows from Mk on perturbed -> the attention output a."""
+        C, d = h.shape[1], self.dim_head
+        a = torch.empty(h.shape[0], C, device=h.device, dtype=h.dtype)
+        f1 = self.fold(1, Mk) if n is None else None
+        if f1 is not None:  # the kept rows keep the folded QKV GEMM; the perturbed rows take the norm
+            qkv = f1.gemm(h[:Mk])
+            npert = ops.layer_norm(h[Mk:], *self._nrm(1))
+        else:
+            if n is None:
+                n = ops.layer_norm(h, *self._nrm(1))
+            qkv = ops.gemm(n[:Mk], self.attn1._wqkv)
+            npert = n[Mk:]
+        ops.attention(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], n_img_k, self.heads, hw, hw, d,
+                      scale=self.attn1.attn_scale, out=a[:Mk])
+        ops.gemm(npert, self.attn1._wqkv[2 * C:], out=a[Mk:])
+        return a
+
     # spatial: tokens are (image, pixel) rows
     # run_*: `n` = norm1(h) when the caller's GEMM already produced it (ops.gemm_ln: the
     # LayerNorm fused into the epilogue of the GEMM writing h, or run right after it)
@@ -215,15 +249,20 @@ class BasicTransformerBlock(nn.Module):
         C = h.shape[1]
         d = self.dim_head
         with ops.plan_scaled(2) if dup else contextlib.nullcontext():
-            f1 = self.fold(1, h.shape[0]) if n is None else None
-            if f1 is not None:
-                qkv = f1.gemm(h)
+            Mk = self._pag_kept(self.attn1, h.shape[0], ctx.batch, ctx.pag_batch)
+            if Mk < h.shape[0]:
+                assert not dup
+                a = self._pag_spatial(h, n, Mk, n_img * Mk // h.shape[0], hw)
             else:
-                if n is None:
-                    n = ops.layer_norm(h, *self._nrm(1))
-                qkv = ops.gemm(n, self.attn1._wqkv)
-            a = ops.attention(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], n_img, self.heads, hw, hw, d,
-                              scale=self.attn1.attn_scale)
+                f1 = self.fold(1, h.shape[0]) if n is None else None
+                if f1 is not None:
+                    qkv = f1.gemm(h)
+                else:
+                    if n is None:
+                        n = ops.layer_norm(h, *self._nrm(1))
+                    qkv = ops.gemm(n, self.attn1._wqkv)
+                a = ops.attention(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], n_img, self.heads, hw, hw, d,
+                                  scale=self.attn1.attn_scale)
             h, n = self._out_norm(a, self.attn1, 2, h)
             q = self.fold(2, h.shape[0]).gemm(h) if n is None else ops.gemm(n, self.attn2._wq)
         kv = None if ctx.kv_cache is None else ctx.kv_cache.get(id(self.attn2))
@@ -271,39 +310,59 @@ class BasicTransformerBlock(nn.Module):
         return out, n
 
     # temporal: tokens are (video, frame, position) rows; attention over frames
-    def run_temporal(self, h, batch, frames, positions, n=None):
+    def run_temporal(self, h, batch, frames, positions, n=None, pag_batch=0):
+        """pag_batch: the last pag_batch videos are PAG's perturbed branch (Ctx.pag_batch)."""
         C = h.shape[1]
-        d = self.dim_head
         pe = self.pos_embed._pe
         mshape = (batch, frames, positions)
         for attn, i in ((self.attn1, 1), (self.attn2, 2)):
-            # Q/K/V projection fused into the attention where the kernel takes the shape
-            # (level 1: 16 frames, d 40), with norm i + PE folded in when the caller left the rows
-            # un-normalised; else the norm, the QKV GEMM and the attention kernel
-            tf = self.temporal_fold(i, *mshape) if n is None else None
-            a = None
-            if tf is not None and tf[0] == "m":
-                mf = tf[1]
-                a = ops.motion_qkv_attention(h, mf.w, batch, frames, positions, self.heads, d,
-                                             scale=attn.attn_scale, ln_fold=(mf.tab, mf.eps))
-            elif self.fuse_qkv_attention and tf is None:
-                if n is None:
-                    n = ops.layer_norm(h, *self._nrm(i), pe=pe, pe_div=positions, pe_period=frames)
-                a = ops.motion_qkv_attention(n, attn._wqkv, batch, frames, positions, self.heads, d,
-                                             scale=attn.attn_scale)
-            if a is None:
-                if tf is not None and tf[0] == "p":  # norm i + PE folded into the QKV GEMM
-                    qkv = tf[1].gemm(h, pe_div=positions, pe_period=frames)
-                else:
-                    if n is None:
-                        n = ops.layer_norm(h, *self._nrm(i), pe=pe, pe_div=positions, pe_period=frames)
-                    qkv = ops.gemm(n, attn._wqkv)
-                a = ops.temporal_attention(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], batch, frames,
-                                           positions, self.heads, d, scale=attn.attn_scale)
+            Mk = self._pag_kept(attn, h.shape[0], batch, pag_batch)
+            if Mk < h.shape[0]:
+                # the kept videos: the plain path at the smaller batch (its own fold decision); the
+                # perturbed ones: V of norm i + PE, through the unfused GEMM
+                a = torch.empty(h.shape[0], C, device=h.device, dtype=h.dtype)
+                self._temporal_attention(attn, i, h[:Mk], None if n is None else n[:Mk], batch - pag_batch, frames,
+                                         positions, out=a[:Mk])
+                npert = n[Mk:] if n is not None else ops.layer_norm(h[Mk:], *self._nrm(i), pe=pe, pe_div=positions,
+                                                                    pe_period=frames)
+                ops.gemm(npert, attn._wqkv[2 * C:], out=a[Mk:])
+            else:
+                a = self._temporal_attention(attn, i, h, n, batch, frames, positions)
             # norm2 (+ PE) after attn1, norm3 after attn2
             h, n = self._out_norm(a, attn, i + 1, h, mshape=mshape, pe=pe if i == 1 else None, pe_div=positions,
                                   pe_period=frames)
         return self._ff(h, n)
+
+    def _temporal_attention(self, attn, i, h, n, batch, frames, positions, out=None):
+        """Self-attention i of a temporal block over (batch, frames, positions) rows -> its output
+        before to_out.  n = norm i (+ PE) of h, or None when the caller left the rows un-normalised."""
+        C = h.shape[1]
+        d = self.dim_head
+        pe = self.pos_embed._pe
+        # Q/K/V projection fused into the attention where the kernel takes the shape
+        # (level 1: 16 frames, d 40), with norm i + PE folded in when the caller left the rows
+        # un-normalised; else the norm, the QKV GEMM and the attention kernel
+        tf = self.temporal_fold(i, batch, frames, positions) if n is None else None
+        a = None
+        if tf is not None and tf[0] == "m":
+            mf = tf[1]
+            a = ops.motion_qkv_attention(h, mf.w, batch, frames, positions, self.heads, d,
+                                         scale=attn.attn_scale, ln_fold=(mf.tab, mf.eps), out=out)
+        elif self.fuse_qkv_attention and tf is None:
+            if n is None:
+                n = ops.layer_norm(h, *self._nrm(i), pe=pe, pe_div=positions, pe_period=frames)
+            a = ops.motion_qkv_attention(n, attn._wqkv, batch, frames, positions, self.heads, d,
+                                         scale=attn.attn_scale, out=out)
+        if a is None:
+            if tf is not None and tf[0] == "p":  # norm i + PE folded into the QKV GEMM
+                qkv = tf[1].gemm(h, pe_div=positions, pe_period=frames)
+            else:
+                if n is None:
+                    n = ops.layer_norm(h, *self._nrm(i), pe=pe, pe_div=positions, pe_period=frames)
+                qkv = ops.gemm(n, attn._wqkv)
+            a = ops.temporal_attention(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], batch, frames,
+                                       positions, self.heads, d, scale=attn.attn_scale, out=out)
+        return a
 
     def run_temporal_gathered(self, h, batch, frames_local, positions, dist):
         """run_temporal on a frame-sharded rank's rows (b, f_loc, p) under the K/V all-gather
@@ -512,6 +571,9 @@ class AnimateDiffTransformer3D(nn.Module):
         B, Fl = ctx.batch, ctx.frames
         dist = ctx.dist
         fn = self._free_noise_windows(Fl, dist)
+        if ctx.pag_batch and (fn is not None or dist is not None):
+            raise NotImplementedError("perturbed-attention guidance with FreeNoise windows or frame sharding is not "
+                                      "supported: the perturbed branch must be whole videos at the end of the batch")
         if fn is not None:
             # the motion norm over all frames, proj_in as a plain GEMM (its norm1 + PE epilogue
             # indexes the PE by absolute frame), then the block on the windows as B * nW videos
@@ -558,7 +620,7 @@ class AnimateDiffTransformer3D(nn.Module):
             else:
                 h, n = ops.gemm_ln(hn, self.proj_in._w, *blk._nrm(1), bias=self.proj_in._b, pe=blk.pos_embed._pe,
                                    pe_div=hw, pe_period=Fl)
-            h = blk.run_temporal(h, B, Fl, hw, n=n)
+            h = blk.run_temporal(h, B, Fl, hw, n=n, pag_batch=ctx.pag_batch)
         else:
             h = ops.gemm(hn, self.proj_in._w, bias=self.proj_in._b)
             if dist.window == "kv-gather":

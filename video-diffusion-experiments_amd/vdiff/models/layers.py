@@ -417,6 +417,11 @@ class Attention(nn.Module):
     # exp-only path).  `attn_scale` is the scale to hand them.
     attn_scale = 1.0 / math.log2(math.e)
 
+    # perturbed-attention guidance: set on a self-attention by UNetMotionModel.set_pag_applied_layers;
+    # the block then runs the perturbed rows of a batch (Ctx.pag_batch) with an identity attention
+    # map, i.e. through to_v and to_out alone (BasicTransformerBlock._pag_spatial / run_temporal)
+    pag = False
+
     def prepare(self):
         c = self.dim_head ** -0.5 * math.log2(math.e)
         wq = self.to_q.weight.float() * c

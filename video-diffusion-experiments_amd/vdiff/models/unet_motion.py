@@ -13,6 +13,7 @@ model to the GPU (done lazily by forward).
 """
 from __future__ import annotations
 
+import re
 from collections import namedtuple
 from typing import Optional
 
@@ -24,7 +25,7 @@ from ..config import down_block_plan, get_config, up_block_plan
 from .blocks import (FREE_NOISE_WEIGHTING_SCHEMES, AnimateDiffTransformer3D, CrossAttnDownBlockMotion,
                      CrossAttnUpBlockMotion, Ctx, DownBlockMotion, ResnetBlock2D, UNetMidBlockCrossAttnMotion,
                      UpBlockMotion)
-from .layers import (Act, Conv2d, GroupNorm, SiLU, TimestepEmbedding, Timesteps, add, bf, f32, fmap_rows, rows_fmap,
+from .layers import (Act, Attention, Conv2d, GroupNorm, SiLU, TimestepEmbedding, Timesteps, add, bf, f32, fmap_rows, rows_fmap,
                      token_rows)
 
 
@@ -46,6 +47,30 @@ def fmap_rows_f32(x):
     return x.permute(0, 2, 3, 1).reshape(-1, x.shape[1])
 
 CIN_PAD = 8  # conv_in input channels padded 4 -> 8 (16-byte NHWC rows)
+
+
+def pag_layer_matches(layer_id: str, name: str) -> bool:
+    """diffusers' PAGMixin._set_pag_attn_processor rule for one self-attention module name: the
+    layer id is a regular expression applied with re.search, and an id that ends in digits must
+    not be followed by another digit ("down_blocks.1" does not select "down_blocks.10...")."""
+    pattern = f"(?:{layer_id})(?![0-9])" if layer_id[-1:].isdigit() else layer_id
+    return re.search(pattern, name) is not None
+
+
+def pag_select(layers, self_attn_names):
+    """The self-attention names `layers` (a layer id or a list of them) select, in module order.
+    A layer id that selects none raises ValueError naming it."""
+    layers = [layers] if isinstance(layers, str) else list(layers)
+    names = list(self_attn_names)
+    picked = set()
+    for layer_id in layers:
+        if not isinstance(layer_id, str) or not layer_id:
+            raise ValueError(f"pag_applied_layers holds {layer_id!r}: each entry is a non-empty string")
+        hit = [n for n in names if pag_layer_matches(layer_id, n)]
+        if not hit:
+            raise ValueError(f"Cannot find PAG layer to set attention processor for: {layer_id}")
+        picked.update(hit)
+    return [n for n in names if n in picked]
 
 
 class ControlResiduals:
@@ -131,10 +156,12 @@ class UNetMotionModel(nn.Module):
         return self
 
     # ------------------------------------------------------------------ core
-    def make_ctx(self, t_emb_bf16, ehs_rows, batch, frames, ctx_len, kv_cache=None, ip_rows=None):
+    def make_ctx(self, t_emb_bf16, ehs_rows, batch, frames, ctx_len, kv_cache=None, ip_rows=None, pag_batch=0):
         temb_silu = self.time_embedding.forward_silu(t_emb_bf16)
         temb_all = ops.gemm(temb_silu, self._w_temb, bias=self._b_temb, out_f32=True)
-        return Ctx(batch, frames, temb_all, ehs_rows, ctx_len, dist=self.dist, kv_cache=kv_cache, ip_rows=ip_rows)
+        ctx = Ctx(batch, frames, temb_all, ehs_rows, ctx_len, dist=self.dist, kv_cache=kv_cache, ip_rows=ip_rows)
+        ctx.pag_batch = pag_batch
+        return ctx
 
     # ------------------------------------------------------------------ IP-Adapter
     def spatial_cross_attentions(self):
@@ -203,6 +230,28 @@ class UNetMotionModel(nn.Module):
         """Every parameter back to its base tensor, bit for bit."""
         from .. import lora
         lora.unload(self)
+
+    # ------------------------------------------------------------------ perturbed-attention guidance
+    def self_attention_names(self):
+        """The diffusers module names of every self-attention: attn1 of the spatial transformer
+        blocks, attn1 and attn2 of the motion modules' (cross-attentions are never perturbed)."""
+        return [n for n, m in self.named_modules() if isinstance(m, Attention) and not m.is_cross]
+
+    def set_pag_applied_layers(self, layers):
+        """Mark the self-attentions PAG perturbs (diffusers' PAGMixin.set_pag_applied_layers +
+        _set_pag_attn_processor; pag_select has the matching rule) and return their names.  None or
+        an empty list clears the marks.  A marked attention runs the perturbed videos of a batch
+        (Ctx.pag_batch, set by DenoiseLoop(pag=...)) through to_v and to_out alone; everything else,
+        the hooked module path included, is unchanged."""
+        names = pag_select(layers, self.self_attention_names()) if layers else []
+        chosen = set(names)
+        for n, m in self.named_modules():
+            if isinstance(m, Attention):
+                m.pag = n in chosen
+        return names
+
+    def pag_applied_layers(self):
+        return [n for n, m in self.named_modules() if isinstance(m, Attention) and m.pag]
 
     # ------------------------------------------------------------------ FreeU
     def enable_freeu(self, s1, s2, b1, b2):

@@ -748,25 +748,78 @@ def unpack_nhwc(src, B, Cc, Fr, H, W, out=None):
     return out
 
 
-def ddim_cfg_step(eps, ncfg, guidance, latents, coef, step_idx=None, x0_out=None, next_in=None):
+STEP_PAG = 0x800  # VD_STEP_PAG, OR-ed into either step's ncfg: perturbed-attention guidance
+
+
+def pag_prefix(n_steps):
+    """Floats of the PAG prefix of a step's coef buffer: n_steps scales, padded to a multiple of 4."""
+    return (n_steps + 3) // 4 * 4
+
+
+def pag_scales(scales):
+    """The per-step PAG scales as a validated fp32 CPU tensor: finite and >= 0, or ValueError (the
+    C side cannot read a device table, include/vdiff.h)."""
+    t = torch.as_tensor(scales, dtype=torch.float32).detach().cpu().reshape(-1)
+    if t.numel() == 0 or not bool(torch.isfinite(t).all()) or bool((t < 0).any()):
+        raise ValueError(f"PAG scales must be a non-empty list of finite values >= 0, got {t.tolist()}")
+    return t
+
+
+def pag_coef(scales, coef):
+    """The coef buffer of a VD_STEP_PAG step: the validated scales, zero padding to a multiple of 4
+    floats, then `coef` (the scheduler's rows, or rows and slabs) flattened, in one fp32 buffer on
+    coef's device.  Pass it to a step op with pag_n=len(scales)."""
+    t = pag_scales(scales)
+    body = coef.reshape(-1)
+    if body.dtype != torch.float32:
+        raise ValueError("pag_coef: coef must be fp32")
+    out = torch.zeros(pag_prefix(t.numel()) + body.numel(), device=coef.device, dtype=torch.float32)
+    out[:t.numel()].copy_(t)
+    out[pag_prefix(t.numel()):].copy_(body)
+    return out
+
+
+def _pag_split(name, coef, pag_n, ncfg):
+    """(flag word, coef body) of a step op: with pag_n > 0, coef is pag_coef's flat buffer."""
+    if not pag_n:
+        return ncfg, coef
+    if coef.dtype != torch.float32 or coef.dim() != 1 or not coef.is_contiguous() or \
+            coef.numel() <= pag_prefix(pag_n):
+        raise ValueError(f"{name}: with pag_n={pag_n}, coef is the flat fp32 buffer of ops.pag_coef "
+                         f"({pag_prefix(pag_n)} floats of scales, then the scheduler's table)")
+    return ncfg | STEP_PAG, coef[pag_prefix(pag_n):]
+
+
+def _pag_rows(name, n, pag_n):
+    if pag_n and n != pag_n:
+        raise ValueError(f"{name}: {pag_n} PAG scales in front of a table of {n} steps")
+
+
+def ddim_cfg_step(eps, ncfg, guidance, latents, coef, step_idx=None, x0_out=None, next_in=None, pag_n=0):
+    """pag_n > 0: perturbed-attention guidance (VD_STEP_PAG) — eps holds ncfg = 2 or 3 branches, the
+    last one perturbed, and coef is ops.pag_coef(scales, rows) with pag_n scales.  Likewise below."""
     _dev(eps, latents, coef, step_idx, x0_out, next_in)
     if latents.dtype != torch.float32 or not latents.is_contiguous():
         raise ValueError("latents must be contiguous fp32")
     B, Cc, Fr, H, W = latents.shape
+    ncfg, body = _pag_split("ddim_cfg_step", coef, pag_n, ncfg)
+    _pag_rows("ddim_cfg_step", body.numel() // 4, pag_n)
     check(lib().vd_ddim_cfg_step(_p(eps), eps.stride(0), ncfg, guidance, _p(latents), B, Cc, Fr, H, W,
-                                 _p(coef), coef.numel() // 4, _p(step_idx), _p(x0_out), _p(next_in),
+                                 _p(coef), body.numel() // 4, _p(step_idx), _p(x0_out), _p(next_in),
                                  next_in.shape[1] if next_in is not None else 0, _stream()),
           "vd_ddim_cfg_step")
 
 
-def euler_cfg_step(eps, ncfg, guidance, latents, coef, step_idx=None, x0_out=None, next_in=None):
+def euler_cfg_step(eps, ncfg, guidance, latents, coef, step_idx=None, x0_out=None, next_in=None, pag_n=0):
     """CFG combine + EulerDiscreteScheduler.step (+ next input's scale_model_input), fused."""
     _dev(eps, latents, coef, step_idx, x0_out, next_in)
     if latents.dtype != torch.float32 or not latents.is_contiguous():
         raise ValueError("latents must be contiguous fp32")
     B, Cc, Fr, H, W = latents.shape
+    ncfg, body = _pag_split("euler_cfg_step", coef, pag_n, ncfg)
+    _pag_rows("euler_cfg_step", body.numel() // 4, pag_n)
     check(lib().vd_euler_cfg_step(_p(eps), eps.stride(0), ncfg, guidance, _p(latents), B, Cc, Fr, H, W,
-                                  _p(coef), coef.numel() // 4, _p(step_idx), _p(x0_out), _p(next_in),
+                                  _p(coef), body.numel() // 4, _p(step_idx), _p(x0_out), _p(next_in),
                                   next_in.shape[1] if next_in is not None else 0, _stream()),
           "vd_euler_cfg_step")
 
@@ -780,7 +833,7 @@ def lcm_buffer_numel(n_steps, latent_numel):
     return n_steps * (LCM_ROW + latent_numel)
 
 
-def lcm_cfg_step(eps, ncfg, guidance, latents, coef, step_idx=None, x0_out=None, next_in=None):
+def lcm_cfg_step(eps, ncfg, guidance, latents, coef, step_idx=None, x0_out=None, next_in=None, pag_n=0):
     """CFG combine + LCMScheduler.step, fused (vd_ddim_cfg_step with VD_STEP_LCM).  `coef` is the
     rows-plus-slabs buffer of include/vdiff.h: n rows of 8 floats, then n noise slabs of
     latents.numel() floats; n is derived from its size.  x0_out receives diffusers' `denoised`."""
@@ -789,13 +842,15 @@ def lcm_cfg_step(eps, ncfg, guidance, latents, coef, step_idx=None, x0_out=None,
         raise ValueError("latents must be contiguous fp32")
     if coef.dtype != torch.float32 or not coef.is_contiguous():
         raise ValueError("lcm_cfg_step: coef must be a contiguous fp32 buffer")
+    ncfg, body = _pag_split("lcm_cfg_step", coef, pag_n, ncfg)
     per = LCM_ROW + latents.numel()
-    if coef.numel() == 0 or coef.numel() % per:
-        raise ValueError(f"lcm_cfg_step: coef holds {coef.numel()} floats, not a multiple of "
+    if body.numel() == 0 or body.numel() % per:
+        raise ValueError(f"lcm_cfg_step: coef holds {body.numel()} floats, not a multiple of "
                          f"{LCM_ROW} + {latents.numel()} (rows, then one noise slab per row)")
+    _pag_rows("lcm_cfg_step", body.numel() // per, pag_n)
     B, Cc, Fr, H, W = latents.shape
     check(lib().vd_ddim_cfg_step(_p(eps), eps.stride(0), ncfg | STEP_LCM, guidance, _p(latents), B, Cc, Fr, H, W,
-                                 _p(coef), coef.numel() // per, _p(step_idx), _p(x0_out), _p(next_in),
+                                 _p(coef), body.numel() // per, _p(step_idx), _p(x0_out), _p(next_in),
                                  next_in.shape[1] if next_in is not None else 0, _stream()),
           "vd_ddim_cfg_step (VD_STEP_LCM)")
 
@@ -810,13 +865,15 @@ def dpm_buffer_numel(n_steps, latent_numel, sde):
     return n_steps * (DPM_ROW + (latent_numel if sde else 0))
 
 
-def dpm_cfg_step(eps, ncfg, guidance, latents, coef, step_idx=None, x0_out=None, next_in=None):
+def dpm_cfg_step(eps, ncfg, guidance, latents, coef, step_idx=None, x0_out=None, next_in=None, pag_n=0):
     """CFG combine + DPMSolverMultistepScheduler.step, fused (vd_ddim_cfg_step with VD_STEP_DPM).
     `coef` is the buffer of include/vdiff.h.  Its shape tells which of the two layouts it has:
     [n, 8] is a table of rows alone (the deterministic type: no row of it may carry the SDE
     flag, whose slab the kernel would look for behind the rows); a flat buffer holds n rows and
     then n noise slabs of latents.numel() floats, n derived from its size.
-    x0_out is required: the history, the previous step's x0 on entry and this step's on exit."""
+    x0_out is required: the history, the previous step's x0 on entry and this step's on exit.
+    With pag_n > 0 the buffer is flat either way and pag_n tells the layouts apart: pag_n rows
+    alone, or pag_n rows and pag_n slabs."""
     _dev(eps, latents, coef, step_idx, x0_out, next_in)
     if latents.dtype != torch.float32 or not latents.is_contiguous():
         raise ValueError("latents must be contiguous fp32")
@@ -826,7 +883,13 @@ def dpm_cfg_step(eps, ncfg, guidance, latents, coef, step_idx=None, x0_out=None,
             or x0_out.numel() != latents.numel():
         raise ValueError("dpm_cfg_step: x0_out (the multistep history, in and out) must be a contiguous fp32 "
                          "tensor of the latents' size")
-    if coef.dim() == 2:
+    ncfg, body = _pag_split("dpm_cfg_step", coef, pag_n, ncfg)
+    if pag_n:
+        if body.numel() not in (pag_n * DPM_ROW, pag_n * (DPM_ROW + latents.numel())):
+            raise ValueError(f"dpm_cfg_step: behind {pag_n} PAG scales coef holds {body.numel()} floats, neither "
+                             f"{pag_n} rows of {DPM_ROW} nor those and {pag_n} slabs of {latents.numel()}")
+        n = pag_n
+    elif coef.dim() == 2:
         if coef.shape[1] != DPM_ROW or coef.shape[0] == 0:
             raise ValueError(f"dpm_cfg_step: a 2-D coef is [n, {DPM_ROW}] rows, got {tuple(coef.shape)}")
         n = coef.shape[0]

@@ -65,6 +65,7 @@ conditioning embedding depends on no timestep and is computed once per call.
 """
 from __future__ import annotations
 
+import math
 import zlib
 from collections import namedtuple
 from pathlib import Path
@@ -126,12 +127,33 @@ class SyntheticTextEncoder:
         return torch.randn((self.seq_len, self.dim), generator=g)
 
 
+class PerturbedAttentionGuidance:
+    """The two numbers of diffusers' PAGMixin: pag_scale and pag_adaptive_scale.  scale_at(t) is
+    its _get_pag_scale — max(pag_scale - pag_adaptive_scale * (1000 - t), 0) under adaptive scaling
+    (pag_adaptive_scale > 0), else pag_scale — evaluated in fp64 and rounded to fp32 once, in the
+    device table (diffusers evaluates it on the step's timestep tensor)."""
+
+    def __init__(self, scale: float = 3.0, adaptive_scale: float = 0.0):
+        self.scale, self.adaptive_scale = float(scale), float(adaptive_scale)
+        if not (math.isfinite(self.scale) and self.scale > 0) or not (math.isfinite(self.adaptive_scale)
+                                                                      and self.adaptive_scale >= 0):
+            raise ValueError(f"PAG needs pag_scale > 0 and pag_adaptive_scale >= 0, got {scale!r}, {adaptive_scale!r}")
+
+    def scale_at(self, t) -> float:
+        if self.adaptive_scale > 0:
+            return max(self.scale - self.adaptive_scale * (1000 - float(t)), 0.0)
+        return self.scale
+
+    def table(self, timesteps):
+        return [self.scale_at(t) for t in torch.as_tensor(timesteps).tolist()]
+
+
 class DenoiseLoop:
     """Preallocated device state + the captured graph of one denoising step."""
 
     def __init__(self, unet: UNetMotionModel, scheduler, latents: torch.Tensor,
                  prompt_embeds: torch.Tensor, guidance_scale: float, timesteps=None,
-                 use_graph: bool = True, cfg_shard=None, ip_embeds=None, step_noise=None, control=None):
+                 use_graph: bool = True, cfg_shard=None, ip_embeds=None, step_noise=None, control=None, pag=None):
         """step_noise (a stochastic scheduler only, where it is required): the noise of the
         stochastic steps in step order.  LCM: [n_steps - 1 or n_steps, B, C, F, H, W] (the last
         step adds none; a row given for it is ignored).  The SDE type of
@@ -147,6 +169,15 @@ class DenoiseLoop:
         K/V cache of its own, and its residuals are added after the UNet's mid block, scaled by the
         [capacity][n] table behind the control block's header — whose first word is this loop's
         device step counter.  Not supported under frame or CFG sharding.
+        pag (PerturbedAttentionGuidance): perturbed-attention guidance.  The UNet batch gains one
+        branch, the LAST one, in which the self-attentions marked by
+        unet.set_pag_applied_layers(...) use an identity attention map: 3 branches
+        [uncond; cond; perturbed] under CFG, 2 branches [cond; perturbed] without.  prompt_embeds
+        (and ip_embeds) hold one entry per branch, the perturbed one the conditional embeddings
+        again: [neg, pos, pos] or [pos, pos].  The step kernel combines the branches
+        (VD_STEP_PAG) with the step's PAG scale, which it reads by the device step index from the
+        table in front of coef, so adaptive scaling replays on the one captured graph.  Not
+        supported with cfg_shard, frame sharding, FreeNoise or ControlNet.
         cfg_shard (vdiff.dist.CfgShard, CFG only): this rank runs the UNet on ONE half
         (cfg_shard.index: 0 uncond, 1 cond) and swaps eps rows with its pair before the
         fused CFG+scheduler update, which both ranks apply to their replicated latents
@@ -155,12 +186,25 @@ class DenoiseLoop:
             unet.prepare()
         dev = unet.device
         self.unet = unet
-        self.ncfg = 2 if guidance_scale > 1 else 1
+        # guidance branches through the UNet: the CFG pair or the one conditional pass, and PAG's
+        # perturbed branch behind them
+        n_cfg = 2 if guidance_scale > 1 else 1
+        self.pag = pag
+        if pag is not None:
+            what = ("cfg_shard" if cfg_shard is not None else "frame sharding (dist=)" if unet.dist is not None else
+                    "FreeNoise" if unet.free_noise_enabled else "ControlNet" if control is not None else None)
+            if what is not None:
+                raise NotImplementedError(f"perturbed-attention guidance with {what} is not supported: the "
+                                          "perturbed branch is whole videos at the end of one rank's UNet batch")
+            if not unet.pag_applied_layers():
+                raise ValueError("DenoiseLoop(pag=...): no self-attention is marked; call "
+                                 "unet.set_pag_applied_layers(...) first")
+        self.ncfg = n_cfg + (pag is not None)
         self.g = float(guidance_scale)
         self.lat = latents.to(dev, torch.float32).contiguous().clone()
         self.B, _, self.F, self.H, self.W = self.lat.shape
         self.Bt = self.ncfg * self.B
-        self.cfg_shard = cfg_shard if self.ncfg == 2 else None
+        self.cfg_shard = cfg_shard if n_cfg == 2 else None
         ts = scheduler.timesteps if timesteps is None else timesteps
         self.scheduler = scheduler
         self.n_steps = len(ts)
@@ -208,6 +252,16 @@ class DenoiseLoop:
         if self.kind == "dpm":
             self.x0_hist = torch.empty_like(self.lat)
             self.step_kwargs = dict(x0_out=self.x0_hist)
+        if pag is not None:
+            # the same buffer with the PAG scales in front (ops.pag_coef): re-point the views
+            width = self.coef_rows.shape[1]
+            self.coef = ops.pag_coef(pag.table(ts), self.coef)
+            body = self.coef[ops.pag_prefix(self.capacity):]
+            self.pag_tab = self.coef[:self.capacity]
+            self.coef_rows = body[:width * self.capacity].view(self.capacity, width)
+            if hasattr(self, "noise_slabs"):
+                self.noise_slabs = body[width * self.capacity:].view(self.capacity, *self.lat.shape)
+            self.step_kwargs["pag_n"] = self.capacity
         self.in_div0 = 1.0
         if self.kind == "euler":
             self.in_div0 = scheduler.input_divisor(scheduler.index_for_timestep(float(torch.as_tensor(ts)[0])))
@@ -230,7 +284,8 @@ class DenoiseLoop:
             self.ctrl_block, self.step_idx = ops.ctrl_block(control.table(self.capacity, self.cn_res), dev)
         pe = prompt_embeds.to(dev, torch.bfloat16).contiguous()
         if pe.shape[0] != self.Bt:
-            raise ValueError(f"prompt_embeds batch {pe.shape[0]} != {self.Bt} (uncond first when CFG)")
+            raise ValueError(f"prompt_embeds batch {pe.shape[0]} != {self.Bt} (uncond first when CFG; with pag= the "
+                             "conditional embeddings once more at the end)")
         self.L = pe.shape[1]
         # the UNet batch: both CFG halves, or this rank's half under cfg_shard
         self.Bu = self.Bt
@@ -294,8 +349,10 @@ class DenoiseLoop:
     def step(self):
         u = self.unet
         te = ops.timestep_embed(self.ts, u.time_proj.num_channels, step_idx=self.step_idx, batch=self.Bu)
-        ctx = u.make_ctx(te, self.ehs_rows, self.Bu, self.F, self.L, kv_cache=self.kv_cache, ip_rows=self.ip_rows)
-        ctx.cfg_dup = self.cfg_dedup and self.Bu == self.Bt == 2 * self.B  # x_in = [lat; lat]
+        ctx = u.make_ctx(te, self.ehs_rows, self.Bu, self.F, self.L, kv_cache=self.kv_cache, ip_rows=self.ip_rows,
+                         pag_batch=self.B if self.pag is not None else 0)
+        # x_in = [lat; lat]; not under PAG, whose last branch differs from the first self-attention on
+        ctx.cfg_dup = self.cfg_dedup and self.Bu == self.Bt == 2 * self.B and self.pag is None
         state = None
         if self.control is not None:  # every row of te is the step's one timestep
             cn = self.control.controlnet
@@ -348,6 +405,8 @@ class DenoiseLoop:
         self.coef_rows[:n].copy_(self.scheduler.coefficient_table(ts.cpu()).to(self.coef.device))
         if self.kind == "euler":
             self.in_div0 = self.scheduler.input_divisor(self.scheduler.index_for_timestep(float(ts[0])))
+        if self.pag is not None:  # the new timesteps' PAG scales
+            self.pag_tab[:n].copy_(ops.pag_scales(self.pag.table(ts)))
         if self.control is not None:  # the new schedule's scales, by its own step count
             ops.ctrl_table(self.ctrl_block, self.cn_res)[:n].copy_(self.control.table(n, self.cn_res))
         self.n_steps = n
@@ -1259,3 +1318,92 @@ class AnimateDiffControlNetPipeline(AnimateDiffPipeline):
                                     num_inference_steps=num_inference_steps, guidance_scale=guidance_scale, **kwargs)
         finally:
             self._control = None
+
+
+class AnimateDiffPAGPipeline(AnimateDiffPipeline):
+    """diffusers AnimateDiffPAGPipeline (PAGMixin): perturbed-attention guidance.  Every step runs
+    one more branch through the UNet in which the self-attentions selected by pag_applied_layers
+    use an identity attention map (their output is the V projection), and the step kernel adds
+    pag_scale * (eps_cond - eps_perturbed) to the (CFG-combined) eps: DenoiseLoop(pag=).  Layer ids
+    follow diffusers: regular expressions searched in the attention modules' names, self-attentions
+    only, so the default "mid_block.*attn1" selects the mid block's spatial attn1 and its motion
+    module's attn1.  It runs with all four schedulers, FreeU, FreeInit, LoRA and IP-Adapter.
+    Refused: a frame-sharded pipeline (dist=), FreeNoise; DenoiseLoop also refuses cfg_shard and
+    ControlNet.  With pag_scale = 0 (or no layers) a call is AnimateDiffPipeline's, untouched.
+    Parity to diffusers is unpinned (diffusers is not a dependency); tests/pag_ref.py restates it."""
+
+    def __init__(self, unet, scheduler=None, text_encoder=None, vae=None, dist=None, tokenizer=None,
+                 pag_applied_layers="mid_block.*attn1"):
+        super().__init__(unet, scheduler, text_encoder=text_encoder, vae=vae, dist=dist, tokenizer=tokenizer)
+        self._pag_scale, self._pag_adaptive_scale = 3.0, 0.0
+        self.set_pag_applied_layers(pag_applied_layers)
+
+    @classmethod
+    def from_config(cls, config="full", device="cuda", seed=0, scheduler=None, dist=None, vae="auto",
+                    pag_applied_layers="mid_block.*attn1"):
+        base = AnimateDiffPipeline.from_config(config, device=device, seed=seed, scheduler=scheduler, dist=dist, vae=vae)
+        pipe = cls(base.unet, base.scheduler, vae=base.vae, dist=dist, pag_applied_layers=pag_applied_layers)
+        pipe.torch_dtype = base.torch_dtype
+        return pipe
+
+    @classmethod
+    def from_pretrained(cls, pretrained_model_name_or_path, motion_adapter=None,
+                        pag_applied_layers="mid_block.*attn1", **kwargs):
+        base = AnimateDiffPipeline.from_pretrained(pretrained_model_name_or_path, motion_adapter=motion_adapter,
+                                                   **kwargs)
+        pipe = cls(base.unet, base.scheduler, vae=base.vae, dist=base.dist, tokenizer=base.tokenizer,
+                   text_encoder=base.text_encoder if base.tokenizer is not None else None,
+                   pag_applied_layers=pag_applied_layers)
+        pipe.torch_dtype = base.torch_dtype
+        return pipe
+
+    def set_pag_applied_layers(self, pag_applied_layers):
+        """diffusers' PAGMixin.set_pag_applied_layers: a layer id or a list of them (strings); the
+        UNet's matching self-attentions are marked at once, and an id that matches none raises
+        ValueError (diffusers raises it at the first call)."""
+        layers = [pag_applied_layers] if isinstance(pag_applied_layers, str) else list(pag_applied_layers or [])
+        if not all(isinstance(x, str) for x in layers):
+            raise ValueError(f"pag_applied_layers must be a string or a list of strings, got {pag_applied_layers!r}")
+        self.unet.set_pag_applied_layers(layers)
+        self.pag_applied_layers = layers
+
+    @property
+    def pag_scale(self) -> float:
+        return self._pag_scale
+
+    @property
+    def pag_adaptive_scale(self) -> float:
+        return self._pag_adaptive_scale
+
+    @property
+    def do_pag_adaptive_scaling(self) -> bool:
+        return self._pag_adaptive_scale > 0 and self._pag_scale > 0 and len(self.pag_applied_layers) > 0
+
+    @property
+    def do_perturbed_attention_guidance(self) -> bool:
+        return self._pag_scale > 0 and self._pag_adaptive_scale >= 0 and len(self.pag_applied_layers) > 0
+
+    def _make_loop(self, unet, scheduler, latents, ehs, guidance_scale, ip_embeds=None, **kwargs):
+        if not self.do_perturbed_attention_guidance:
+            return DenoiseLoop(unet, scheduler, latents, ehs, guidance_scale, ip_embeds=ip_embeds, **kwargs)
+        # the perturbed branch takes the conditional embeddings: [neg, pos, pos] or [pos, pos]
+        B = latents.shape[0]
+        ehs = torch.cat([ehs, ehs[-B:]])
+        if ip_embeds is not None:
+            ip_embeds = torch.cat([ip_embeds, ip_embeds[-B:]])
+        # another pipeline on the same UNet may have marked other layers since
+        unet.set_pag_applied_layers(self.pag_applied_layers)
+        pag = PerturbedAttentionGuidance(self._pag_scale, self._pag_adaptive_scale)
+        return DenoiseLoop(unet, scheduler, latents, ehs, guidance_scale, ip_embeds=ip_embeds, pag=pag, **kwargs)
+
+    @torch.no_grad()
+    def __call__(self, *args, pag_scale: float = 3.0, pag_adaptive_scale: float = 0.0, **kwargs):
+        self._pag_scale, self._pag_adaptive_scale = float(pag_scale), float(pag_adaptive_scale)
+        if self.do_perturbed_attention_guidance:
+            if self.dist is not None:
+                raise NotImplementedError("AnimateDiffPAGPipeline with a frame-sharded pipeline (dist=) is not "
+                                          "supported: the perturbed branch is whole videos of one rank's UNet batch")
+            if self.free_noise_enabled:
+                raise NotImplementedError("perturbed-attention guidance with FreeNoise is not supported: the windows "
+                                          "ride on the batch axis of the temporal kernels; disable_free_noise()")
+        return super().__call__(*args, **kwargs)
