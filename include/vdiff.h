@@ -689,6 +689,27 @@ int vd_block_transpose(const void* src, void* dst, int64_t nb, int64_t na, int64
  *   outside 1..64; i >= ldy; any bit above the column byte; y_period < 1; C % 8; x == out; y not
  *   inside a device allocation (hipPointerGetAttributes: every thread reads the step word through
  *   it, and a plain op 7 with host operands stays refused as it was before the op existed).
+ *   Op 8, VD_ROWS_SPARSE_COND, builds SparseCtrl's condition rows (diffusers'
+ *   AnimateDiffSparseControlNetPipeline.prepare_sparse_control_conditioning: zeros, the key frames
+ *   assigned at controlnet_frame_indices, and a mask channel that is 1 on those frames), riding
+ *   here for the same reason as ops 2-7.  op = VD_ROWS_SPARSE_COND | VD_ROWS_SPARSE_CH(cc), cc the
+ *   number of condition channels, 1..7 (the low byte is the op; 4 = a VAE latent, 3 = pixels).
+ *   The output is the packed NHWC rows the conv loaders take: C == 8 bf16 columns.  Geometry:
+ *   F = y_period frames, hw = y_div positions per frame, K = ldy key frames per video, rows =
+ *   B * F * hw OUTPUT rows.  x = bf16 rows of stride ldx >= 8, key frame k of video b at rows
+ *   (b * K + k) * hw + p; only columns < cc are read, whatever columns cc..7 hold never reaches
+ *   the output.  y = K int32 frame indices in DEVICE memory, 4-byte aligned, y_f32 == 1 (4-byte
+ *   words, as op 7's step word), read inside the launch only.  For video b, frame f, position p,
+ *   with k* the LARGEST k whose idx[k] == f (the last assignment wins, as in torch indexing):
+ *     out[(b * F + f) * hw + p] = { x[(b * K + k*) * hw + p][0..cc), bf16 1.0, +0 ... }  if k* exists,
+ *                                 { +0 x 8 }                                           otherwise.
+ *   The cc channels are copied bit for bit.  An index outside [0, F) matches no frame (the host
+ *   wrapper refuses it).  A gather: every output row looks its frame up in a table of the K
+ *   indices; no scatter, no atomics, one 16-byte store per row, every output element written.
+ *   VD_EINVAL, before any launch: cc == 0 (a plain op 8) or cc > 7 or any bit above the channel
+ *   byte; C != 8; K or F outside 1..256; hw < 1; rows not a multiple of F * hw; x or out NULL or
+ *   not 16-byte aligned; out == x; ldx or ldo below 8 or not a multiple of 8; y NULL, misaligned,
+ *   y_f32 != 1 or not inside a device allocation (hipPointerGetAttributes, as op 7).
  * vd_upsample_nearest2x: rows of n_img h x w images -> rows of their nearest x2 upsample
  *   (Upsample2D's F.interpolate(scale_factor=2.0, mode="nearest")). */
 enum {
@@ -699,11 +720,13 @@ enum {
   VD_ROWS_WIN_GATHER = 4,
   VD_ROWS_WIN_MERGE = 5,
   VD_ROWS_SPECTRAL = 6,
-  VD_ROWS_CTRL_ADD = 7
+  VD_ROWS_CTRL_ADD = 7,
+  VD_ROWS_SPARSE_COND = 8
 };
 #define VD_ROWS_WIN_STRIDE(s) ((s) << 8)
 #define VD_ROWS_SPEC_PASS(p) ((p) << 8)
 #define VD_ROWS_CTRL_COL(i) ((i) << 8)
+#define VD_ROWS_SPARSE_CH(cc) ((cc) << 8)
 #define VD_SPECTRAL_MAX 256
 int vd_rows_eltwise(int32_t op, const void* x, int64_t ldx, const void* y, int64_t ldy, int32_t y_f32,
                     int64_t y_div, int64_t y_period, int64_t rows, int64_t C, void* out, int64_t ldo,

@@ -27,7 +27,8 @@ __device__ __forceinline__ void load8_any(const void* p, int is_f32, float* f) {
 // op 0: out[r] = (x ? x[r] : 0) + y[(r / y_div) % y_period]     (y bf16 or fp32)
 // op 1: out[r] = silu(x[r])
 // op 3: out[r] = x[r] * *y                                        (y one fp32 on the device)
-// (op 2 is freeu_filter_kernel, ops 4 and 5 win_gather_kernel / win_merge_kernel, op 7 ctrl_add_kernel below)
+// (op 2 is freeu_filter_kernel, ops 4 and 5 win_gather_kernel / win_merge_kernel, op 7 ctrl_add_kernel,
+// op 8 sparse_cond_kernel below)
 __global__ void rows_eltwise_kernel(int op, const bf16_t* x, int64_t ldx, const void* y, int64_t ldy, int y_f32,
                                     int64_t y_div, int64_t y_period, int64_t rows, int64_t C, bf16_t* out,
                                     int64_t ldo) {
@@ -323,6 +324,44 @@ __global__ __launch_bounds__(NT) void ctrl_add_kernel(const bf16_t* x, int64_t l
   }
 }
 
+// op 8, SparseCtrl's condition rows: out row (b, f, p) <- key frame k* of video b, k* the LARGEST k
+// with idx[k] == f, its cc channels as they are, bf16 1.0 in column cc (the conditioning mask), +0
+// above; a frame no index names is +0 in all 8 columns (include/vdiff.h).  A gather: every workgroup
+// first turns the K indices into a frame -> k* table in LDS (thread f scans the indices in ascending
+// k, so the last assignment wins whatever the launch geometry; an index outside [0, F) matches no
+// thread), then one lane per output row does one 16-byte load (conditioned frames only) and one
+// 16-byte store.  No scatter, no atomics; every output element is written.
+constexpr int SPARSE_MAX = 256;  // the longest F and K: F <= NT fills the table in one pass
+__global__ __launch_bounds__(NT) void sparse_cond_kernel(const bf16_t* x, int64_t ldx, const int* idx, int K, int F,
+                                                         int64_t hw, int cc, int64_t rows, bf16_t* out, int64_t ldo) {
+  __shared__ int kof[SPARSE_MAX];
+  for (int f = threadIdx.x; f < F; f += NT) {
+    int ks = -1;
+    for (int k = 0; k < K; ++k)
+      if (idx[k] == f) ks = k;
+    kof[f] = ks;
+  }
+  __syncthreads();
+  for (int64_t r = (int64_t)blockIdx.x * NT + threadIdx.x; r < rows; r += (int64_t)gridDim.x * NT) {
+    const int64_t bf = r / hw, p = r - bf * hw, b = bf / F;
+    const int ks = kof[(int)(bf - b * F)];
+    uint4 v = make_uint4(0, 0, 0, 0);
+    if (ks >= 0) {
+      const uint4 u = *(const uint4*)(x + ((b * K + ks) * hw + p) * ldx);
+      const uint32_t in[4] = {u.x, u.y, u.z, u.w};
+      uint32_t o[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {  // columns 2j (low half) and 2j + 1 (high half)
+        const uint32_t lo = 2 * j < cc ? (in[j] & 0xffffu) : (2 * j == cc ? 0x3f80u : 0u);
+        const uint32_t hi = 2 * j + 1 < cc ? (in[j] & 0xffff0000u) : (2 * j + 1 == cc ? 0x3f800000u : 0u);
+        o[j] = lo | hi;
+      }
+      v = make_uint4(o[0], o[1], o[2], o[3]);
+    }
+    *(uint4*)(out + r * ldo) = v;
+  }
+}
+
 unsigned grid_for(int64_t total) {
   const int64_t b = (total + NT - 1) / NT;
   return (unsigned)(b < 16384 ? (b > 0 ? b : 1) : 16384);
@@ -367,6 +406,22 @@ extern "C" int vd_rows_eltwise(int32_t op, const void* x, int64_t ldx, const voi
     hipLaunchKernelGGL(ctrl_add_kernel, dim3(grid_for(rows * (C / 8))), dim3(NT), 0, (hipStream_t)stream,
                        (const bf16_t*)x, ldx, (const float*)y, (int)ldy, (int)col, (int)y_period, rows, C,
                        (bf16_t*)out, ldo);
+    return vd_launch_status();
+  }
+  // op 8 carries its channel count above the low byte (VD_ROWS_SPARSE_CH); a plain op 8 carries 0 and
+  // stays refused, a bit above the channel byte makes cc > 7
+  if (op >= 0 && (op & 0xff) == VD_ROWS_SPARSE_COND) {
+    const int32_t cc = op >> 8;
+    const int64_t F = y_period, hw = y_div, K = ldy;
+    VD_CHECK_ARG(cc >= 1 && cc <= 7 && C == 8);
+    VD_CHECK_ARG(K >= 1 && K <= SPARSE_MAX && F >= 1 && F <= SPARSE_MAX && hw >= 1 && rows > 0 && hw <= rows);
+    VD_CHECK_ARG(rows % (F * hw) == 0);
+    VD_CHECK_ARG(x && out && al16(x) && al16(out) && x != out);
+    VD_CHECK_ARG(ldx >= 8 && ldo >= 8 && ldx % 8 == 0 && ldo % 8 == 0);
+    // the K indices must be DEVICE memory, as op 7's control block: every workgroup reads them
+    VD_CHECK_ARG(y && ((uintptr_t)y & 3) == 0 && y_f32 == 1 && on_device(y));
+    hipLaunchKernelGGL(sparse_cond_kernel, dim3(grid_for(rows)), dim3(NT), 0, (hipStream_t)stream, (const bf16_t*)x,
+                       ldx, (const int*)y, (int)K, (int)F, hw, (int)cc, rows, (bf16_t*)out, ldo);
     return vd_launch_status();
   }
   // ops 4 and 5 carry the window stride above the low byte (VD_ROWS_WIN_STRIDE); no other op does

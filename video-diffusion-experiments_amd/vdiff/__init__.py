@@ -7,6 +7,7 @@ experiments) over hand-written gfx950 HIP kernels in libvdiff_hip.so.
 from .config import FULL, TINY, get_config  # noqa: F401
 from .models import UNetMotionModel, UNetMotionOutput  # noqa: F401
 from .models.controlnet import ControlNetModel, ControlNetOutput  # noqa: F401
+from .models.sparse_controlnet import SparseControlNetModel  # noqa: F401
 from .models.clip import CLIPTextModel, CLIPTextModelOutput  # noqa: F401
 from .models.clip import CLIPVisionModelWithProjection, ImageProjection  # noqa: F401
 from .image_processor import CLIPImageProcessor  # noqa: F401
@@ -15,8 +16,9 @@ from .models.vae import (AutoencoderKL, AutoencoderKLOutput, DecoderOutput,  # n
                          DiagonalGaussianDistribution)
 from .pretrained import MotionAdapter  # noqa: F401
 from .pipeline import (AnimateDiffControlNetPipeline, AnimateDiffPAGPipeline, AnimateDiffPipeline,  # noqa: F401
-                       AnimateDiffPipelineOutput, AnimateDiffVideoToVideoPipeline, ControlNetConditioning,
-                       DenoiseLoop, PerturbedAttentionGuidance)
+                       AnimateDiffPipelineOutput, AnimateDiffSparseControlNetPipeline,
+                       AnimateDiffVideoToVideoPipeline, ControlNetConditioning, DenoiseLoop,
+                       PerturbedAttentionGuidance, SparseControlConditioning)
 from .sched import (DDIMScheduler, DDIMSchedulerOutput, DPMSolverMultistepScheduler,  # noqa: F401
                     DPMSolverMultistepSchedulerOutput, EulerDiscreteScheduler, EulerDiscreteSchedulerOutput,
                     LCMScheduler, LCMSchedulerOutput)

@@ -1086,6 +1086,54 @@ def ctrl_add_(acc, res, block, col, cols=None):
     return acc
 
 
+ROWS_SPARSE_COND = 8         # VD_ROWS_SPARSE_COND
+ROWS_SPARSE_CH_SHIFT = 8     # VD_ROWS_SPARSE_CH(cc) = cc << 8, cc in 1..7
+SPARSE_MAX = 256             # the longest F and K
+
+
+def sparse_frame_indices(idx, F):
+    """controlnet_frame_indices the Python way: negative indices count from the end, anything
+    outside [-F, F) is an IndexError (torch indexing's), before any device work."""
+    idx = idx.tolist() if torch.is_tensor(idx) else list(idx)
+    out = []
+    for i in idx:
+        if isinstance(i, bool) or int(i) != i:
+            raise TypeError(f"sparse_cond: frame index {i!r} is not an integer")
+        i = int(i)
+        if not -F <= i < F:
+            raise IndexError(f"sparse_cond: frame index {i} is out of bounds for {F} frames")
+        out.append(i + F if i < 0 else i)
+    return out
+
+
+def sparse_cond(key_rows, idx, B, F, hw, cc, out=None):
+    """SparseCtrl's condition rows (vd_rows_eltwise op 8): key_rows holds K = len(idx) key frames
+    per video as bf16 NHWC rows (b, k, p) of >= 8 columns, of which the first cc are the condition;
+    the result is the [B * F * hw, 8] packed rows of B videos of F frames: frame idx[k] takes key
+    frame k (the last k that names a frame wins) with 1.0 in column cc, every other frame is zero.
+    One launch writes every element: no zero fill, no indexed copies."""
+    frames = sparse_frame_indices(idx, F)
+    K = len(frames)
+    if not 1 <= K <= SPARSE_MAX or not 1 <= F <= SPARSE_MAX:
+        raise ValueError(f"sparse_cond: 1..{SPARSE_MAX} key frames and frames, got {K} and {F}")
+    if not 1 <= cc <= 7:
+        raise ValueError(f"sparse_cond: 1..7 condition channels, got {cc}")
+    _dev(key_rows, out)
+    if key_rows.shape[0] != B * K * hw or key_rows.shape[1] != 8:
+        raise ValueError(f"sparse_cond: key rows of shape {tuple(key_rows.shape)} are not {B} videos x {K} key frames "
+                         f"x {hw} positions of 8 columns")
+    if out is None:
+        out = torch.empty(B * F * hw, 8, device=key_rows.device, dtype=BF16)
+    if tuple(out.shape) != (B * F * hw, 8):
+        raise ValueError(f"sparse_cond: out of shape {tuple(out.shape)}, {B} videos of {F} frames need "
+                         f"{(B * F * hw, 8)}")
+    idx_dev = torch.tensor(frames, dtype=torch.int32, device=key_rows.device)
+    check(lib().vd_rows_eltwise(ROWS_SPARSE_COND | (cc << ROWS_SPARSE_CH_SHIFT), _p(key_rows), _rows(key_rows),
+                                _p(idx_dev), K, 1, hw, F, out.shape[0], 8, _p(out), _rows(out), _stream()),
+          "vd_rows_eltwise(sparse_cond)")
+    return out
+
+
 ROWS_SPECTRAL = 6            # VD_ROWS_SPECTRAL
 ROWS_SPEC_PASS_SHIFT = 8     # VD_ROWS_SPEC_PASS(p) = p << 8, p in 1..5
 SPECTRAL_MAX = 256           # VD_SPECTRAL_MAX: the longest F, H or W

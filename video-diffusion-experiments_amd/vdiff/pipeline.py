@@ -62,6 +62,12 @@ captured graph and its 13 residuals are added to the UNet's skips and mid-block 
 `ops.ctrl_add_`, whose scale is read on the device from a [steps][13] table by the step index —
 control_guidance_start / end and guess mode change it between replays, not the graph.  The
 conditioning embedding depends on no timestep and is computed once per call.
+
+AnimateDiffSparseControlNetPipeline (diffusers' fifth AnimateDiff pipeline, SparseCtrl) conditions
+the video on a few key frames: `ops.sparse_cond` (vd_rows_eltwise op 8) builds the condition rows
+with their mask column in one launch, a `vdiff.SparseControlNetModel` — the UNet's encoder with its
+motion modules, which reads no latents — embeds them once per call and runs inside the captured
+graph through the same `control=` path, with one scale for every step.
 """
 from __future__ import annotations
 
@@ -75,6 +81,7 @@ import torch
 from . import ops
 from .models.clip import CLIPTextModel
 from .models.controlnet import ControlNetModel, control_scale_table
+from .models.sparse_controlnet import SparseControlNetModel
 from .models.unet_motion import CIN_PAD, UNetMotionModel
 from .models.vae import AutoencoderKL
 from .sched.ddim import DDIMScheduler
@@ -96,6 +103,51 @@ class ControlNetConditioning:
 
     def table(self, n_steps, n_res):
         return control_scale_table(n_steps, n_res, self.scale, self.guess_mode, self.start, self.end)
+
+    @property
+    def reads_latents(self) -> bool:
+        """Whether the ControlNet's forward_rows takes the step's latent rows in front of the
+        condition rows (SparseControlNetModel reads no latents)."""
+        return getattr(self.controlnet, "reads_latents", True)
+
+    def condition_rows(self, B, F, H, W):
+        """The rows DenoiseLoop hands to forward_rows at every step, for B videos of F frames of
+        H x W latents: computed once, they depend on no timestep."""
+        fr = self.frames
+        if fr.dim() != 5 or fr.shape[0] not in (1, B) or fr.shape[2] != F or tuple(fr.shape[3:]) != (8 * H, 8 * W):
+            raise ValueError(f"conditioning frames of shape {tuple(fr.shape)}: expected (1 or {B}, 3, {F}, "
+                             f"{8 * H}, {8 * W})")
+        return self.controlnet.embed_condition(fr.expand(B, -1, -1, -1, -1))
+
+
+class SparseControlConditioning(ControlNetConditioning):
+    """DenoiseLoop(control=) for a SparseControlNetModel: the packed condition rows of
+    ops.sparse_cond — n_videos (1, shared by the batch, or the batch) videos of `frames` frames of
+    h x w condition pixels, the mask in column conditioning_channels — and the scale, which holds
+    at every step (diffusers' sparse pipeline has no guidance window); guess mode weighs the
+    residuals.  from_tensors takes diffusers' (B, C, F, h, w) condition and (B, 1, F, h, w) mask."""
+
+    def __init__(self, controlnet, cond_rows, n_videos, frames, h, w, scale=1.0, guess_mode=False):
+        super().__init__(controlnet, None, scale, guess_mode, 0.0, 1.0)
+        if cond_rows.dim() != 2 or tuple(cond_rows.shape) != (n_videos * frames * h * w, CIN_PAD):
+            raise ValueError(f"condition rows of shape {tuple(cond_rows.shape)}: expected "
+                             f"{(n_videos * frames * h * w, CIN_PAD)}")
+        self.cond_rows, self.geometry = cond_rows, (n_videos, frames, h, w)
+
+    @classmethod
+    def from_tensors(cls, controlnet, controlnet_cond, conditioning_mask, scale=1.0, guess_mode=False):
+        B, _, Fr, h, w = controlnet_cond.shape
+        return cls(controlnet, controlnet.condition_rows(controlnet_cond, conditioning_mask), B, Fr, h, w, scale,
+                   guess_mode)
+
+    def condition_rows(self, B, F, H, W):
+        n, fr, h, w = self.geometry
+        ds = self.controlnet.condition_downscale
+        if n not in (1, B) or fr != F or (h, w) != (ds * H, ds * W):
+            raise ValueError(f"sparse condition of {n} videos x {fr} frames x {h} x {w}: expected 1 or {B} videos x "
+                             f"{F} frames x {ds * H} x {ds * W}")
+        emb = self.controlnet.embed_condition(self.cond_rows, n * F, h, w)
+        return emb if n == B else emb.repeat(B, 1)
 
 
 class ControlState:
@@ -272,6 +324,9 @@ class DenoiseLoop:
                 raise NotImplementedError("ControlNet under frame sharding (dist=) or CFG sharding (cfg_shard=) is "
                                           "not supported: the residuals are not sharded over the ranks")
             cn = control.controlnet
+            if not control.reads_latents and unet.free_noise_enabled:
+                raise NotImplementedError("FreeNoise with a SparseControlNetModel is not supported: the ControlNet's "
+                                          "own motion modules would need the windows too; disable_free_noise()")
             if not cn._prepared:
                 cn.prepare()
             self.cn_res = cn.num_residuals
@@ -311,12 +366,7 @@ class DenoiseLoop:
         self.x_in = self.x_in2[:self.Bu * self.F * self.H * self.W]
         self.kv_cache = {}
         if control is not None:
-            fr = control.frames
-            if fr.dim() != 5 or fr.shape[0] not in (1, self.B) or fr.shape[2] != self.F or \
-                    tuple(fr.shape[3:]) != (8 * self.H, 8 * self.W):
-                raise ValueError(f"conditioning frames of shape {tuple(fr.shape)}: expected (1 or {self.B}, 3, {self.F}, "
-                                 f"{8 * self.H}, {8 * self.W})")
-            cond = control.controlnet.embed_condition(fr.expand(self.B, -1, -1, -1, -1))
+            cond = control.condition_rows(self.B, self.F, self.H, self.W)
             # guess mode under CFG: the ControlNet sees the conditional half only
             self.cn_cond_only = control.guess_mode and self.ncfg == 2
             self.cn_batch = self.B if self.cn_cond_only else self.Bt
@@ -358,7 +408,10 @@ class DenoiseLoop:
             cn = self.control.controlnet
             cctx = cn.make_ctx(te[:self.cn_batch], self.cn_ehs_rows, self.cn_batch, self.F, self.L,
                                kv_cache=self.cn_kv_cache)
-            res = cn.forward_rows(self.cn_x_in, self.cn_cond_rows, self.H, self.W, cctx)
+            if self.control.reads_latents:
+                res = cn.forward_rows(self.cn_x_in, self.cn_cond_rows, self.H, self.W, cctx)
+            else:  # SparseCtrl: timestep, text and condition only
+                res = cn.forward_rows(self.cn_cond_rows, self.H, self.W, cctx)
             state = ControlState(res, self.ctrl_block, self.cn_cond_only)
         eps = u.forward_rows(self.x_in, self.H, self.W, ctx, control=state)
         if self.cfg_shard is not None:
@@ -1316,6 +1369,201 @@ class AnimateDiffControlNetPipeline(AnimateDiffPipeline):
         try:
             return super().__call__(prompt=prompt, num_frames=num_frames, height=height, width=width,
                                     num_inference_steps=num_inference_steps, guidance_scale=guidance_scale, **kwargs)
+        finally:
+            self._control = None
+
+
+def decode_key_frames(frames, height=None, width=None):
+    """SparseCtrl's conditioning_frames -> (K, 3, H, W) fp32 in [0, 1] on the CPU: a list of PIL
+    images, a list of (H, W, 3) arrays or (3, H, W) tensors, an (K, H, W, 3) array or an (K, 3, H, W)
+    tensor; one image alone is K = 1.  PIL images of another size than height x width are resized,
+    arrays and tensors refused (decode_video_frames)."""
+    import numpy as np
+    if isinstance(frames, (list, tuple)) and len(frames) > 0:
+        if isinstance(frames[0], np.ndarray):
+            frames = np.stack([np.asarray(f) for f in frames])
+        elif torch.is_tensor(frames[0]):
+            frames = torch.stack(list(frames))
+    elif not isinstance(frames, (list, tuple, np.ndarray)) and not torch.is_tensor(frames):
+        frames = [frames]  # one PIL image
+    x = decode_video_frames(frames, height, width)
+    if x.shape[0] != 1:
+        raise ValueError("conditioning_frames: one list of key frames (per-video key frames are not supported)")
+    return x[0]
+
+
+class AnimateDiffSparseControlNetPipeline(AnimateDiffPipeline):
+    """diffusers AnimateDiffSparseControlNetPipeline (SparseCtrl): `pipe(prompt=, conditioning_frames=,
+    controlnet_frame_indices=[0, 8, 15], ...)` conditions the video on a few key frames.  The key
+    frames — VAE latents for an RGB checkpoint (use_simplified_condition_embedding), the [0, 1]
+    images for a scribble one — become the condition rows with their mask column in one launch
+    (ops.sparse_cond), the conditioning embedding runs once per call, and a SparseControlNetModel,
+    which reads no latents, runs inside the captured graph of every step (DenoiseLoop(control=)).
+    IP-Adapter, FreeU, LoRA and the DDIM, Euler, LCM and DPM schedulers combine with it as with the
+    plain pipeline.  Refused: a list of ControlNets, dist=, cfg_shard, FreeInit, FreeNoise.
+    Parity to diffusers is unpinned, as the UNet's."""
+
+    vae_encoder = True  # from_config: the RGB variant encodes its key frames
+
+    def __init__(self, unet, controlnet, scheduler=None, text_encoder=None, vae=None, dist=None, tokenizer=None):
+        if isinstance(controlnet, (list, tuple)):
+            raise NotImplementedError("a list of ControlNets (MultiControlNetModel) is not supported: pass one")
+        if not isinstance(controlnet, SparseControlNetModel):
+            raise ValueError("AnimateDiffSparseControlNetPipeline needs controlnet=vdiff.SparseControlNetModel(...)")
+        if dist is not None:
+            raise NotImplementedError("AnimateDiffSparseControlNetPipeline with a frame-sharded pipeline (dist=) is "
+                                      "not supported: the ControlNet's motion modules need every frame of a video")
+        super().__init__(unet, scheduler, text_encoder=text_encoder, vae=vae, dist=dist, tokenizer=tokenizer)
+        self.controlnet = controlnet
+        self._control = None  # the running call's SparseControlConditioning arguments
+
+    @classmethod
+    def from_config(cls, config="full", device="cuda", seed=0, scheduler=None, dist=None, vae="auto",
+                    controlnet_seed=1, use_simplified_condition_embedding=True):
+        """Synthetic-weight pipeline: AnimateDiffPipeline.from_config's with the VAE's encoder, plus
+        a synthetic SparseControlNetModel of the same config (its zero convs are NOT zero, or it
+        would be invisible)."""
+        if dist is not None:
+            raise NotImplementedError("AnimateDiffSparseControlNetPipeline with a frame-sharded pipeline (dist=) is "
+                                      "not supported")
+        base = AnimateDiffPipeline.from_config(config, device=device, seed=seed, scheduler=scheduler, vae=None)
+        if vae == "auto":
+            vae = config if config in ("tiny", "full") else None
+        if isinstance(vae, str):
+            vae = init_synthetic_(AutoencoderKL(vae, encoder=True), seed).to(device=device, dtype=torch.bfloat16).prepare()
+        base.vae = vae
+        extra = {} if use_simplified_condition_embedding else dict(use_simplified_condition_embedding=False,
+                                                                   conditioning_channels=3)
+        cn = init_synthetic_(SparseControlNetModel(config, **extra), controlnet_seed)
+        cn = cn.to(device=device, dtype=torch.bfloat16)
+        pipe = cls(base.unet, cn.prepare(), base.scheduler, vae=base.vae)
+        pipe.torch_dtype = base.torch_dtype
+        return pipe
+
+    @classmethod
+    def from_pretrained(cls, pretrained_model_name_or_path, controlnet=None, motion_adapter=None, **kwargs):
+        """AnimateDiffPipeline.from_pretrained's components plus
+        controlnet=SparseControlNetModel.from_pretrained(...)."""
+        if controlnet is None:
+            raise ValueError("AnimateDiffSparseControlNetPipeline needs "
+                             "controlnet=SparseControlNetModel.from_pretrained(...)")
+        if isinstance(controlnet, (list, tuple)):
+            raise NotImplementedError("a list of ControlNets (MultiControlNetModel) is not supported: pass one")
+        if kwargs.get("dist") is not None:
+            raise NotImplementedError("AnimateDiffSparseControlNetPipeline with a frame-sharded pipeline (dist=) is "
+                                      "not supported")
+        base = AnimateDiffPipeline.from_pretrained(pretrained_model_name_or_path, motion_adapter=motion_adapter,
+                                                   **kwargs)
+        if controlnet.device.type == "cuda":
+            controlnet.prepare()
+        pipe = cls(base.unet, controlnet, base.scheduler, vae=base.vae, tokenizer=base.tokenizer,
+                   text_encoder=base.text_encoder if base.tokenizer is not None else None)
+        pipe.torch_dtype = base.torch_dtype
+        return pipe
+
+    # ------------------------------------------------------------------ the condition
+    def _sparse_rows(self, key_frames, num_frames, controlnet_frame_indices):
+        """key_frames (B, C, K, h, w) -> ops.sparse_cond's rows [B * num_frames * h * w, 8]."""
+        cc = self.controlnet.config["conditioning_channels"]
+        if key_frames.dim() != 5 or key_frames.shape[1] != cc:
+            raise ValueError(f"key frames of shape {tuple(key_frames.shape)}: expected (B, {cc}, K, h, w)")
+        idx = list(controlnet_frame_indices)
+        B, _, K, h, w = key_frames.shape
+        if len(idx) > K:
+            raise ValueError(f"{len(idx)} controlnet_frame_indices for {K} conditioning frames")
+        ops.sparse_frame_indices(idx, num_frames)  # IndexError before any device work
+        keys = key_frames[:, :, :len(idx)].to(self.unet.device, torch.float32).contiguous()
+        rows = ops.pack_latents(keys, dup=1, cpad=CIN_PAD)
+        return ops.sparse_cond(rows, idx, B, num_frames, h * w, cc)
+
+    @torch.no_grad()
+    def prepare_sparse_control_conditioning(self, conditioning_frames, num_frames, controlnet_frame_indices,
+                                            device=None, dtype=None):
+        """diffusers' method of that name: conditioning_frames (B, C, K, h, w), K >= len(indices) —
+        VAE latents x scaling_factor for the simplified embedding, [0, 1] images for the full one —
+        -> (controlnet_cond (B, C, F, h, w), conditioning_mask (B, 1, F, h, w)), fp32: zeros, the
+        first len(indices) key frames at their frame indices, the mask 1 there.  One launch of
+        vd_rows_eltwise op 8 builds both."""
+        B, C, _, h, w = conditioning_frames.shape
+        rows = self._sparse_rows(conditioning_frames, num_frames, controlnet_frame_indices)
+        both = ops.unpack_nhwc(rows, B, C + 1, num_frames, h, w)
+        cond, mask = both[:, :C].contiguous(), both[:, C:].contiguous()
+        if device is not None or dtype is not None:
+            cond, mask = cond.to(device=device, dtype=dtype), mask.to(device=device, dtype=dtype)
+        return cond, mask
+
+    @torch.no_grad()
+    def prepare_key_frames(self, images, h, w, generator=None):
+        """(K, 3, H, W) images in [0, 1] -> the key frames (1, C, K, h', w') the ControlNet's
+        embedding takes for h x w latents: the VAE latents x scaling_factor of 2 x - 1 (simplified
+        embedding; the posterior is sampled with the call's generator), or the images themselves."""
+        cn = self.controlnet
+        if cn.simplified:
+            if self.vae is None or getattr(self.vae, "encoder", None) is None:
+                raise ValueError("a SparseControlNetModel with use_simplified_condition_embedding conditions on the "
+                                 "VAE latents of the key frames: AnimateDiffSparseControlNetPipeline needs a VAE "
+                                 "with its encoder, AutoencoderKL(config, encoder=True)")
+            x = (2.0 * images - 1.0).to(self.unet.device)
+            n = self.vae.frames_per_chunk
+            lat = torch.cat([self.vae.encode(x[i:i + n]).latent_dist.sample(generator=generator)
+                             for i in range(0, x.shape[0], n)]) * self.vae.config["scaling_factor"]
+            if tuple(lat.shape[1:]) != (cn.config["conditioning_channels"], h, w):
+                raise ValueError(f"the key frames encode to {tuple(lat.shape[1:])} latents, the video's are "
+                                 f"({cn.config['conditioning_channels']}, {h}, {w}): resize the conditioning frames")
+            return lat.permute(1, 0, 2, 3)[None].float()
+        if tuple(images.shape[1:]) != (cn.config["conditioning_channels"], 8 * h, 8 * w):
+            raise ValueError(f"conditioning frames are {tuple(images.shape[1:])}, the video needs "
+                             f"({cn.config['conditioning_channels']}, {8 * h}, {8 * w})")
+        return images.permute(1, 0, 2, 3)[None].float()
+
+    def _make_loop(self, unet, scheduler, latents, *args, **kwargs):
+        c = self._control
+        if kwargs.get("cfg_shard") is not None:
+            raise NotImplementedError("AnimateDiffSparseControlNetPipeline with cfg_shard is not supported")
+        control = SparseControlConditioning(self.controlnet, c["rows"], *c["geometry"], c["scale"], c["guess_mode"])
+        return DenoiseLoop(unet, scheduler, latents, *args, control=control, **kwargs)
+
+    @torch.no_grad()
+    def __call__(self, prompt=None, num_frames=16, height=None, width=None, num_inference_steps=50,
+                 guidance_scale=7.5, *, conditioning_frames=None, controlnet_conditioning_scale=1.0,
+                 controlnet_frame_indices=(0,), guess_mode=False, generator=None, cfg_shard=None, **kwargs):
+        if self.free_init_enabled:
+            raise NotImplementedError("FreeInit together with SparseCtrl is not supported; disable_free_init()")
+        if self.free_noise_enabled:
+            raise NotImplementedError("FreeNoise together with SparseCtrl is not supported: the ControlNet's own "
+                                      "motion modules would need the windows too; disable_free_noise()")
+        if self.dist is not None:
+            raise NotImplementedError("AnimateDiffSparseControlNetPipeline with a frame-sharded pipeline (dist=) is "
+                                      "not supported")
+        if cfg_shard is not None:
+            raise NotImplementedError("AnimateDiffSparseControlNetPipeline with cfg_shard is not supported")
+        if conditioning_frames is None:
+            raise ValueError("conditioning_frames required: the key frames")
+        if isinstance(controlnet_conditioning_scale, (list, tuple)):
+            raise NotImplementedError("a list of conditioning scales (MultiControlNet) is not supported")
+        mlen = self.controlnet.config["motion_max_seq_length"]
+        if num_frames > mlen:
+            raise ValueError(f"num_frames={num_frames} exceeds the SparseControlNetModel's motion_max_seq_length={mlen}")
+        sample = self.unet.config["sample_size"]
+        height, width = height or sample * 8, width or sample * 8
+        h, w = height // 8, width // 8
+        idx = list(controlnet_frame_indices)
+        ops.sparse_frame_indices(idx, num_frames)
+        # the size the embedding needs: 8 x the latents for images, the VAE's own factor for latents
+        ds = 8
+        if self.controlnet.simplified and self.vae is not None:
+            ds = 2 ** (len(self.vae.config["block_out_channels"]) - 1)
+        images = decode_key_frames(conditioning_frames, ds * h, ds * w)
+        if len(idx) > images.shape[0]:
+            raise ValueError(f"{len(idx)} controlnet_frame_indices for {images.shape[0]} conditioning frames")
+        keys = self.prepare_key_frames(images[:len(idx)], h, w, generator=generator)
+        rows = self._sparse_rows(keys, num_frames, idx)
+        self._control = dict(rows=rows, geometry=(1, num_frames, keys.shape[3], keys.shape[4]),
+                             scale=float(controlnet_conditioning_scale), guess_mode=bool(guess_mode))
+        try:
+            return super().__call__(prompt=prompt, num_frames=num_frames, height=height, width=width,
+                                    num_inference_steps=num_inference_steps, guidance_scale=guidance_scale,
+                                    generator=generator, **kwargs)
         finally:
             self._control = None
 
