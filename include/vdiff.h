@@ -530,8 +530,40 @@ int vd_lpips_pairs(const void* frames_u8, int64_t videos, int32_t frames, int32_
  *   Each thread reads m1[i] before it writes x0[i].  x0_out == NULL or x0_out == latents is
  *   VD_EINVAL.  A first-order row (step 0 of any schedule) never reads it, so the history needs
  *   no clearing between schedules.
- * VD_STEP_PAG OR-ed into ncfg (0x800) of vd_ddim_cfg_step — alone, or with VD_STEP_LCM or
- *   VD_STEP_DPM — or of vd_euler_cfg_step: perturbed-attention guidance (diffusers' PAGMixin).  The
+ * VD_STEP_UNIPC OR-ed into vd_ddim_cfg_step's ncfg (0x2000: 0x200 and 0x1000 stay VD_EINVAL;
+ *   together with VD_STEP_LCM or VD_STEP_DPM it is VD_EINVAL; vd_euler_cfg_step refuses it; with
+ *   VD_STEP_PAG it combines as VD_STEP_DPM does, the PAG scales in front of the rows): the
+ *   diffusers UniPCMultistepScheduler.step update — predict_x0, solver_type "bh1" or "bh2", solver
+ *   order 1 or 2, epsilon prediction — the corrector of the previous step and the predictor of
+ *   this one in one pass, in the same one-rounding-per-op fp32 arithmetic, in exactly this order:
+ *     m_t = (x - sigma_s*eps) / alpha_s
+ *     xc  = x
+ *     flags & 1 (the corrector runs):
+ *       x_  = c_last*S2 - c_m*S0
+ *       d_t = m_t - S0
+ *       r   = flags & 2 ? rho0*((S1 - S0) / rk_c) + rhot*d_t : rhot*d_t
+ *       xc  = x_ - c_B*r
+ *     y = p_x*xc - p_m*m_t
+ *     flags & 4 (a second-order predictor):  y = y - p_B*(0.5*((S0 - m_t) / rk_p))
+ *     latents <- y;  S1 <- S0;  S0 <- m_t;  S2 <- xc;  next_in <- bf16(y) per branch
+ *   both divisions correctly rounded.  coef is 16-byte aligned and holds n_coef rows of 16 floats
+ *     {alpha_s, sigma_s, c_last, c_m, c_B, rk_c, rho0, rhot, p_x, p_m, p_B, rk_p, flags, 0, 0, 0}
+ *     c_last = sig_i/sig_{i-1}, c_m = alpha_i*h_phi_1 and c_B = alpha_i*B_h of the corrector's
+ *     step i-1 -> i; p_x = sig_{i+1}/sig_i, p_m = alpha_{i+1}*h_phi_1 and p_B = alpha_{i+1}*B_h of
+ *     the predictor's step i -> i+1; rk_c, rk_p the ratios of the log-SNR steps (negative);
+ *     (rho0, rhot) the corrector's weights, (0, 0.5) at first order; flags = 1.0 * the corrector
+ *     runs + 2.0 * it is second order + 4.0 * the predictor is second order.  A slot its row does
+ *     not use holds 0.0 and is never read — the kernel never divides by an unused rk — and the
+ *     whole table is finite (a final sigma of 0 gives p_x = 0, p_m = -1: y = m_t).
+ *   x0_out is REQUIRED and is both input and output, the solver's state: THREE contiguous slabs of
+ *   N = B*C*F*H*W floats, S0 the latest x0 prediction, S1 the one before it, S2 `last`, the sample
+ *   the previous predictor started from.  Each thread reads its element of every slab the row
+ *   needs before it writes any, and all three slabs are written on every step.  A row with
+ *   flags 0 (step 0 of any run) reads no slab and starts the history (S1 <- m_t as well); only a
+ *   second-order corrector reads S1; so the state needs no clearing between schedules.
+ *   x0_out == NULL, or [x0_out, x0_out + 3N) overlapping [latents, latents + N), is VD_EINVAL.
+ * VD_STEP_PAG OR-ed into ncfg (0x800) of vd_ddim_cfg_step — alone, or with VD_STEP_LCM,
+ *   VD_STEP_DPM or VD_STEP_UNIPC — or of vd_euler_cfg_step: perturbed-attention guidance (diffusers' PAGMixin).  The
  *   low byte is then 2 or 3 (anything else is VD_EINVAL; without the flag 3 stays VD_EINVAL):
  *     3: eps rows [uncond; cond; perturbed], each of B*F*H*W rows,
  *          e = (e_u + g*(e_c - e_u)) + s*(e_c - e_p)
@@ -543,7 +575,7 @@ int vd_lpips_pairs(const void* frames_u8, int64_t videos, int32_t frames, int32_
  *     n_coef fp32 PAG scales, padded with (-n_coef mod 4) floats to a multiple of 4 (the padding
  *       is never read), then
  *     the scheduler's unchanged layout, from float offset 4*ceil(n_coef/4): n_coef rows of 4
- *       (DDIM, Euler) or 8 (LCM, DPM) floats and, where that scheduler has them, its n_coef noise
+ *       (DDIM, Euler), 8 (LCM, DPM) or 16 (UniPC) floats and, where that scheduler has them, its n_coef noise
  *       slabs behind the rows.  The padding keeps the 16-byte alignment LCM and DPM ask for.
  *   s = pag[st], st the same clamped device step index that picks the coefficient row, read inside
  *   the launch.  The scales must be finite and >= 0; this library cannot read device memory, so
@@ -555,6 +587,7 @@ int vd_lpips_pairs(const void* frames_u8, int64_t videos, int32_t frames, int32_
 enum { VD_STEP_LCM = 0x100 }; /* OR-ed into vd_ddim_cfg_step's ncfg, see above */
 enum { VD_STEP_DPM = 0x400 }; /* likewise; x0_out becomes the in/out history, see above */
 enum { VD_STEP_PAG = 0x800 }; /* into either step's ncfg: a third branch, scales in front of coef */
+enum { VD_STEP_UNIPC = 0x2000 }; /* as VD_STEP_DPM; x0_out becomes the in/out three-slab state, see above */
 int vd_timestep_embed(const float* ts, int64_t n_ts, const int32_t* step_idx, int64_t B,
                       int32_t dim, void* out, vd_stream_t stream);
 int vd_pack_latents(const float* x, int64_t B, int64_t C, int64_t F, int64_t H, int64_t W,

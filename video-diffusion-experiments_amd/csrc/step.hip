@@ -11,7 +11,9 @@
 // captured hipGraph of one step can be replayed for every timestep.  With VD_STEP_LCM in ncfg
 // the same entry point launches the LCMScheduler update, whose per-step noise follows the
 // coefficient rows in the same device buffer (lcm_cfg_kernel); with VD_STEP_DPM the
-// DPMSolverMultistepScheduler update, whose history travels in x0_out (dpm_cfg_kernel).
+// DPMSolverMultistepScheduler update, whose history travels in x0_out (dpm_cfg_kernel); with
+// VD_STEP_UNIPC the UniPCMultistepScheduler update, corrector and predictor in one pass, whose
+// three state slabs travel in x0_out (unipc_cfg_kernel).
 #include "common.h"
 
 namespace {
@@ -258,6 +260,67 @@ __global__ void dpm_cfg_kernel(const float* eps, int64_t ld_eps, int ncfg, float
   }
 }
 
+// CFG combine + diffusers:UniPCMultistepScheduler.step (predict_x0, bh1 / bh2, solver order 1 or 2,
+// epsilon prediction): the corrector of the previous step and the predictor of this one in one
+// pass, in diffusers' fp32 operation order (vd_ddim_cfg_step with VD_STEP_UNIPC in ncfg).
+// coef holds n_coef rows of 16 floats {alpha_s, sigma_s, c_last, c_m, c_B, rk_c, rho0, rhot, p_x,
+// p_m, p_B, rk_p, flags, 0, 0, 0}; flags = 1 the corrector runs + 2 it is second order + 4 the
+// predictor is second order.  A slot its row does not use is 0 and is not read: no division by an
+// unused rk.  state (x0_out) is in/out, three slabs of B*C*F*HW floats: S0 the latest x0
+// prediction, S1 the one before it, S2 `last`, the sample the previous predictor started from.
+//   m_t = (x - sigma_s e) / alpha_s
+//   corrector:  x_ = c_last S2 - c_m S0;  r = [rho0 (S1 - S0) / rk_c +] rhot (m_t - S0);  xc = x_ - c_B r
+//   predictor:  y = p_x xc - p_m m_t [- p_B (0.5 (S0 - m_t) / rk_p)]
+//   lat <- y;  S1 <- S0;  S0 <- m_t;  S2 <- xc
+// Each thread reads its element of every slab before it writes any.  A flags-0 row (step 0 of a
+// run) reads no slab — it starts the history, S1 <- m_t as well — and only a second-order
+// corrector reads S1, so the state needs no clearing between schedules.
+__global__ void unipc_cfg_kernel(const float* eps, int64_t ld_eps, int ncfg, float g, float* lat,
+                                 int64_t B, int64_t C, int64_t F, int64_t HW, const float* coef,
+                                 int64_t n_coef, const int32_t* step_idx, float* state, bf16_t* next_in,
+                                 int64_t cpad, const float* pag) {
+#pragma clang fp contract(off)  // one rounding per operation, as torch's separate fp32 ops
+  const int st = table_row(step_idx, n_coef);
+  const float pag_s = pag ? pag[st] : 0.f;
+  const float* row = coef + 16 * (int64_t)st;
+  const float alpha_s = row[0], sigma_s = row[1], c_last = row[2], c_m = row[3], c_B = row[4];
+  const float rk_c = row[5], rho0 = row[6], rhot = row[7];
+  const float p_x = row[8], p_m = row[9], p_B = row[10], rk_p = row[11];
+  const int flags = (int)row[12];
+  const bool corr = (flags & 1) != 0, corr2 = (flags & 2) != 0, pred2 = (flags & 4) != 0;
+  const int64_t total = B * C * F * HW;
+  const int64_t half_rows = B * F * HW;
+  float* S0 = state;
+  float* S1 = state + total;
+  float* S2 = state + 2 * total;
+  for (int64_t i = (int64_t)blockIdx.x * NT + threadIdx.x; i < total; i += (int64_t)gridDim.x * NT) {
+    const int64_t p = i % HW;
+    const int64_t f = (i / HW) % F;
+    const int64_t c = (i / (HW * F)) % C;
+    const int64_t b = i / (HW * F * C);
+    const int64_t r = (b * F + f) * HW + p;
+    const float e = guided_eps(eps, ld_eps, r, c, half_rows, ncfg, g, pag != nullptr, pag_s);
+    const float x = lat[i];
+    const float m_t = div_rn(x - sigma_s * e, alpha_s);
+    const float m0 = flags ? S0[i] : m_t;
+    float xc = x;
+    if (corr) {
+      const float x_ = c_last * S2[i] - c_m * m0;
+      const float d_t = m_t - m0;
+      float res = rhot * d_t;
+      if (corr2) res = rho0 * div_rn(S1[i] - m0, rk_c) + res;
+      xc = x_ - c_B * res;
+    }
+    float y = p_x * xc - p_m * m_t;
+    if (pred2) y = y - p_B * (0.5f * div_rn(m0 - m_t, rk_p));
+    lat[i] = y;
+    S1[i] = m0;
+    S0[i] = m_t;
+    S2[i] = xc;
+    if (next_in) write_next_in(next_in, f2bf(y), r, c, half_rows, ncfg, C, cpad);
+  }
+}
+
 __global__ void step_advance_kernel(int32_t* step_idx) { *step_idx += 1; }
 
 __global__ void block_transpose_kernel(const bf16_t* src, bf16_t* dst, int64_t nb, int64_t na,
@@ -327,11 +390,11 @@ extern "C" int vd_ddim_cfg_step(const float* eps, int64_t ld_eps, int32_t ncfg, 
                                 float* latents, int64_t B, int64_t C, int64_t F, int64_t H,
                                 int64_t W, const float* coef, int64_t n_coef, const int32_t* step_idx,
                                 float* x0_out, void* next_in, int64_t cpad, vd_stream_t stream) {
-  // VD_STEP_LCM / VD_STEP_DPM ride on ncfg above its low byte; both at once, or any other high
-  // bit but VD_STEP_PAG, are refused
-  const bool lcm = (ncfg & VD_STEP_LCM) != 0, dpm = (ncfg & VD_STEP_DPM) != 0;
-  VD_CHECK_ARG(!(lcm && dpm));
-  ncfg &= ~(VD_STEP_LCM | VD_STEP_DPM);
+  // VD_STEP_LCM / VD_STEP_DPM / VD_STEP_UNIPC ride on ncfg above its low byte; two of them at
+  // once, or any other high bit but VD_STEP_PAG, are refused
+  const bool lcm = (ncfg & VD_STEP_LCM) != 0, dpm = (ncfg & VD_STEP_DPM) != 0, unipc = (ncfg & VD_STEP_UNIPC) != 0;
+  VD_CHECK_ARG(lcm + dpm + unipc <= 1);
+  ncfg &= ~(VD_STEP_LCM | VD_STEP_DPM | VD_STEP_UNIPC);
   const float* pag;
   if (const int rc = split_pag_coef(ncfg, coef, n_coef, pag)) return rc;
   VD_CHECK_ARG(eps && latents && coef && n_coef > 0 && ld_eps >= C);
@@ -353,6 +416,17 @@ extern "C" int vd_ddim_cfg_step(const float* eps, int64_t ld_eps, int32_t ncfg, 
                        coef, n_coef, step_idx, x0_out, (bf16_t*)next_in, cpad, pag);
     return vd_launch_status();
   }
+  if (unipc) {
+    // x0_out is the state: required, in/out, three slabs of the latents' size that do not overlap them
+    VD_CHECK_ARG(B > 0 && C > 0 && F > 0 && H > 0 && W > 0 && ((uintptr_t)coef & 15) == 0);
+    const int64_t total = B * C * F * H * W;
+    VD_CHECK_ARG(x0_out && !((uintptr_t)x0_out < (uintptr_t)(latents + total) &&
+                             (uintptr_t)latents < (uintptr_t)(x0_out + 3 * total)));
+    hipLaunchKernelGGL(unipc_cfg_kernel, dim3(grid_for(total)), dim3(NT), 0,
+                       (hipStream_t)stream, eps, ld_eps, ncfg, guidance, latents, B, C, F, H * W,
+                       coef, n_coef, step_idx, x0_out, (bf16_t*)next_in, cpad, pag);
+    return vd_launch_status();
+  }
   hipLaunchKernelGGL(ddim_cfg_kernel, dim3(grid_for(B * C * F * H * W)), dim3(NT), 0,
                      (hipStream_t)stream, eps, ld_eps, ncfg, guidance, latents, B, C, F, H * W,
                      coef, n_coef, step_idx, x0_out, (bf16_t*)next_in, cpad, pag);
@@ -363,7 +437,7 @@ extern "C" int vd_euler_cfg_step(const float* eps, int64_t ld_eps, int32_t ncfg,
                                  float* latents, int64_t B, int64_t C, int64_t F, int64_t H,
                                  int64_t W, const float* coef, int64_t n_coef, const int32_t* step_idx,
                                  float* x0_out, void* next_in, int64_t cpad, vd_stream_t stream) {
-  // VD_STEP_PAG is the one flag Euler takes; VD_STEP_LCM / VD_STEP_DPM fail the low-byte check
+  // VD_STEP_PAG is the one flag Euler takes; VD_STEP_LCM / VD_STEP_DPM / VD_STEP_UNIPC fail the low-byte check
   const float* pag;
   if (const int rc = split_pag_coef(ncfg, coef, n_coef, pag)) return rc;
   VD_CHECK_ARG(eps && latents && coef && n_coef > 0 && ld_eps >= C);

@@ -21,6 +21,6 @@ from .pipeline import (AnimateDiffControlNetPipeline, AnimateDiffPAGPipeline, An
                        PerturbedAttentionGuidance, SparseControlConditioning)
 from .sched import (DDIMScheduler, DDIMSchedulerOutput, DPMSolverMultistepScheduler,  # noqa: F401
                     DPMSolverMultistepSchedulerOutput, EulerDiscreteScheduler, EulerDiscreteSchedulerOutput,
-                    LCMScheduler, LCMSchedulerOutput)
+                    LCMScheduler, LCMSchedulerOutput, UniPCMultistepScheduler, UniPCMultistepSchedulerOutput)
 from .tokenizer import CLIPTokenizer  # noqa: F401
 from .weights import init_synthetic_, load_diffusers_state_dict  # noqa: F401

@@ -20,6 +20,7 @@ VD_OK, VD_EINVAL, VD_EUNSUPPORTED, VD_ERCCL = 0, 1000, 1001, 1002  # enum vd_sta
 VD_STEP_LCM = 0x100  # OR-ed into vd_ddim_cfg_step's ncfg: the LCMScheduler update (include/vdiff.h)
 VD_STEP_DPM = 0x400  # likewise: the DPMSolverMultistepScheduler update, x0_out its in/out history
 VD_STEP_PAG = 0x800  # into either step's ncfg: perturbed-attention guidance, its scales in front of coef
+VD_STEP_UNIPC = 0x2000  # as VD_STEP_DPM: the UniPCMultistepScheduler update, x0_out its in/out three-slab state
 
 # Every exported symbol and its argtypes: the single source of truth used by the
 # loader and by tests/test_abi.py (which checks it against include/vdiff.h).

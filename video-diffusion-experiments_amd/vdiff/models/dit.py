@@ -243,6 +243,9 @@ class DiTDenoiseLoop:
         ts = scheduler.timesteps
         self.n_steps = len(ts)
         self.ts = torch.as_tensor(ts).to(dev, torch.float32)
+        if getattr(scheduler, "kind", "ddim") == "unipc":
+            raise NotImplementedError("UniPCMultistepScheduler with DiTDenoiseLoop is not supported: this loop "
+                                      "drives the DDIM schedule and holds no multistep state")
         self.coef = scheduler.coefficient_table(torch.as_tensor(ts).cpu()).to(dev)
         self.sched_step = ops.SCHED_STEP[getattr(scheduler, "kind", "ddim")]
         if getattr(scheduler, "kind", "ddim") != "ddim":

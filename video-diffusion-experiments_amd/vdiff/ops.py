@@ -906,7 +906,44 @@ def dpm_cfg_step(eps, ncfg, guidance, latents, coef, step_idx=None, x0_out=None,
           "vd_ddim_cfg_step (VD_STEP_DPM)")
 
 
-SCHED_STEP = {"ddim": ddim_cfg_step, "euler": euler_cfg_step, "lcm": lcm_cfg_step, "dpm": dpm_cfg_step}
+STEP_UNIPC = 0x2000  # VD_STEP_UNIPC, OR-ed into vd_ddim_cfg_step's ncfg
+UNIPC_ROW = 16       # floats per UniPC coefficient row
+
+
+def unipc_cfg_step(eps, ncfg, guidance, latents, coef, step_idx=None, x0_out=None, next_in=None, pag_n=0):
+    """CFG combine + UniPCMultistepScheduler.step — the previous step's corrector and this step's
+    predictor — fused (vd_ddim_cfg_step with VD_STEP_UNIPC).  `coef` is [n, 16] rows
+    (include/vdiff.h); with pag_n > 0 the flat buffer of ops.pag_coef with pag_n such rows.
+    x0_out is required: the solver's state, three slabs of the latents' size ([3, *latents.shape]):
+    the last two x0 predictions and the sample the previous predictor started from, in and out."""
+    _dev(eps, latents, coef, step_idx, x0_out, next_in)
+    if latents.dtype != torch.float32 or not latents.is_contiguous():
+        raise ValueError("latents must be contiguous fp32")
+    if coef.dtype != torch.float32 or not coef.is_contiguous():
+        raise ValueError("unipc_cfg_step: coef must be a contiguous fp32 buffer")
+    if x0_out is None or x0_out.dtype != torch.float32 or not x0_out.is_contiguous() \
+            or x0_out.numel() != 3 * latents.numel():
+        raise ValueError("unipc_cfg_step: x0_out (the solver's state, in and out) must be a contiguous fp32 "
+                         "tensor of three times the latents' size")
+    ncfg, body = _pag_split("unipc_cfg_step", coef, pag_n, ncfg)
+    if pag_n:
+        if body.numel() != pag_n * UNIPC_ROW:
+            raise ValueError(f"unipc_cfg_step: behind {pag_n} PAG scales coef holds {body.numel()} floats, not "
+                             f"{pag_n} rows of {UNIPC_ROW}")
+        n = pag_n
+    else:
+        if coef.dim() != 2 or coef.shape[1] != UNIPC_ROW or coef.shape[0] == 0:
+            raise ValueError(f"unipc_cfg_step: coef is [n, {UNIPC_ROW}] rows, got {tuple(coef.shape)}")
+        n = coef.shape[0]
+    B, Cc, Fr, H, W = latents.shape
+    check(lib().vd_ddim_cfg_step(_p(eps), eps.stride(0), ncfg | STEP_UNIPC, guidance, _p(latents), B, Cc, Fr, H, W,
+                                 _p(coef), n, _p(step_idx), _p(x0_out), _p(next_in),
+                                 next_in.shape[1] if next_in is not None else 0, _stream()),
+          "vd_ddim_cfg_step (VD_STEP_UNIPC)")
+
+
+SCHED_STEP = {"ddim": ddim_cfg_step, "euler": euler_cfg_step, "lcm": lcm_cfg_step, "dpm": dpm_cfg_step,
+              "unipc": unipc_cfg_step}
 
 
 def step_advance(step_idx):

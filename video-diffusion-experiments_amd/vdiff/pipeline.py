@@ -56,6 +56,11 @@ multistep: DenoiseLoop holds the previous step's x0 prediction in `x0_hist`, whi
 reads and overwrites in place, so the state is carried from one graph replay to the next without
 host work.  Its SDE type draws one fp32 noise slab per step, kept behind the rows as LCM's are.
 
+With a `vdiff.UniPCMultistepScheduler` (the predictor-corrector solver, usually 10-20 steps) the
+step kernel runs the previous step's corrector and this step's predictor in one pass; DenoiseLoop
+holds its state — the last two x0 predictions and the sample the previous predictor started from —
+in the three slabs of `unipc_state`, read and overwritten in place like `x0_hist`.
+
 AnimateDiffControlNetPipeline (diffusers' third AnimateDiff pipeline) conditions the video on
 per-frame control images: a `vdiff.ControlNetModel` runs on the step's input inside the same
 captured graph and its 13 residuals are added to the UNet's skips and mid-block output by
@@ -299,11 +304,16 @@ class DenoiseLoop:
                                  f"this loop's is {self.kind!r}")
             self.coef = self.coef_rows = rows.to(dev)
         # a multistep scheduler's state between two replays: the previous step's x0 prediction, which
-        # the step kernel reads and overwrites in place.  Step 0 of a schedule never reads it.
+        # the step kernel reads and overwrites in place.  Step 0 of a schedule never reads it, so
+        # neither reset() nor reschedule() clears it.
         self.step_kwargs = {}
         if self.kind == "dpm":
             self.x0_hist = torch.empty_like(self.lat)
             self.step_kwargs = dict(x0_out=self.x0_hist)
+        elif self.kind == "unipc":
+            # UniPC's: the last two x0 predictions and the sample the previous predictor started from
+            self.unipc_state = torch.empty((3,) + tuple(self.lat.shape), device=dev, dtype=torch.float32)
+            self.step_kwargs = dict(x0_out=self.unipc_state)
         if pag is not None:
             # the same buffer with the PAG scales in front (ops.pag_coef): re-point the views
             width = self.coef_rows.shape[1]
@@ -811,6 +821,10 @@ class AnimateDiffPipeline:
         return getattr(self.scheduler, "kind", None) == "dpm"
 
     @property
+    def _unipc(self) -> bool:
+        return getattr(self.scheduler, "kind", None) == "unipc"
+
+    @property
     def _dpm_sde(self) -> bool:
         return self._dpm and self.scheduler.sde
 
@@ -825,6 +839,10 @@ class AnimateDiffPipeline:
                                       "not sharded over the ranks' frames ('dpmsolver++' is)")
         if self._dpm and self.free_init_enabled:
             raise NotImplementedError("FreeInit with DPMSolverMultistepScheduler is not supported: diffusers' "
+                                      "add_noise at a timestep outside the schedule falls back to the last sigma; "
+                                      "disable_free_init(), or use DDIMScheduler")
+        if self._unipc and self.free_init_enabled:
+            raise NotImplementedError("FreeInit with UniPCMultistepScheduler is not supported: diffusers' "
                                       "add_noise at a timestep outside the schedule falls back to the last sigma; "
                                       "disable_free_init(), or use DDIMScheduler")
 

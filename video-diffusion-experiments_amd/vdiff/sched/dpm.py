@@ -114,6 +114,36 @@ def dpm_row(sigma_prev, sigma_s, sigma_t, second: bool, sde: bool) -> torch.Tens
     return row.float()
 
 
+def build_schedule(config, train_sigmas, num_inference_steps):
+    """diffusers' set_timesteps, which DPMSolverMultistepScheduler and UniPCMultistepScheduler share:
+    n + 1 points for "linspace" and "leading" with the last dropped, n for "trailing"; the sigmas of
+    those timesteps (or Karras' ramp, whose timesteps are the rounded _sigma_to_t), and the final
+    sigma appended -> (n timesteps, n + 1 fp32 sigmas)."""
+    T = config.num_train_timesteps
+    n = int(num_inference_steps)
+    if n < 1 or n > T:
+        raise ValueError(f"num_inference_steps {num_inference_steps}: 1..{T}")
+    sp = config.timestep_spacing
+    if sp == "linspace":
+        ts = np.linspace(0, T - 1, n + 1).round()[::-1][:-1].copy().astype(np.int64)
+    elif sp == "leading":
+        ratio = T // (n + 1)
+        ts = (np.arange(0, n + 1) * ratio).round()[::-1][:-1].copy().astype(np.int64)
+        ts += config.steps_offset
+    else:  # trailing
+        ts = np.arange(T, 0, -(T / n)).round().copy().astype(np.int64)
+        ts -= 1
+    sigmas = train_sigmas.numpy()
+    if config.use_karras_sigmas:
+        log_sigmas = np.log(sigmas)
+        sigmas = DPMSolverMultistepScheduler._convert_to_karras(np.flip(sigmas).copy(), n)
+        ts = np.array([DPMSolverMultistepScheduler._sigma_to_t(s, log_sigmas) for s in sigmas]).round()
+    else:
+        sigmas = np.interp(ts, np.arange(0, len(sigmas)), sigmas)
+    last = float(train_sigmas[0]) if config.final_sigmas_type == "sigma_min" else 0.0
+    return ts, torch.from_numpy(np.concatenate([sigmas, [last]]).astype(np.float32))
+
+
 class DPMSolverMultistepScheduler:
     kind = "dpm"  # selects the fused device update (ops.SCHED_STEP)
     order = 1     # diffusers' scheduler.order: one model call per step
@@ -218,32 +248,8 @@ class DPMSolverMultistepScheduler:
         return t.reshape(sigma.shape)
 
     def set_timesteps(self, num_inference_steps: int, device=None):
-        """diffusers' set_timesteps: n + 1 points for "linspace" and "leading" with the last dropped,
-        n for "trailing"; the sigmas of those timesteps (or Karras' ramp, whose timesteps are the
-        rounded _sigma_to_t), and the final sigma appended — n timesteps, n + 1 fp32 sigmas."""
-        T = self.config.num_train_timesteps
-        n = int(num_inference_steps)
-        if n < 1 or n > T:
-            raise ValueError(f"num_inference_steps {num_inference_steps}: 1..{T}")
-        sp = self.config.timestep_spacing
-        if sp == "linspace":
-            ts = np.linspace(0, T - 1, n + 1).round()[::-1][:-1].copy().astype(np.int64)
-        elif sp == "leading":
-            ratio = T // (n + 1)
-            ts = (np.arange(0, n + 1) * ratio).round()[::-1][:-1].copy().astype(np.int64)
-            ts += self.config.steps_offset
-        else:  # trailing
-            ts = np.arange(T, 0, -(T / n)).round().copy().astype(np.int64)
-            ts -= 1
-        sigmas = self.train_sigmas.numpy()
-        if self.config.use_karras_sigmas:
-            log_sigmas = np.log(sigmas)
-            sigmas = self._convert_to_karras(np.flip(sigmas).copy(), n)
-            ts = np.array([self._sigma_to_t(s, log_sigmas) for s in sigmas]).round()
-        else:
-            sigmas = np.interp(ts, np.arange(0, len(sigmas)), sigmas)
-        last = float(self.train_sigmas[0]) if self.config.final_sigmas_type == "sigma_min" else 0.0
-        self.sigmas = torch.from_numpy(np.concatenate([sigmas, [last]]).astype(np.float32))
+        """diffusers' set_timesteps (build_schedule above): n timesteps, n + 1 fp32 sigmas."""
+        ts, self.sigmas = build_schedule(self.config, self.train_sigmas, num_inference_steps)
         self.timesteps = torch.from_numpy(np.asarray(ts).astype(np.int64)).to(device)
         self.num_inference_steps = len(ts)
         self.model_outputs = [None] * self.config.solver_order
