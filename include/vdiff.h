@@ -562,8 +562,36 @@ int vd_lpips_pairs(const void* frames_u8, int64_t videos, int32_t frames, int32_
  *   flags 0 (step 0 of any run) reads no slab and starts the history (S1 <- m_t as well); only a
  *   second-order corrector reads S1; so the state needs no clearing between schedules.
  *   x0_out == NULL, or [x0_out, x0_out + 3N) overlapping [latents, latents + N), is VD_EINVAL.
+ * VD_STEP_ANCESTRAL OR-ed into vd_euler_cfg_step's ncfg (0x4000: 0x200 and 0x1000 stay VD_EINVAL;
+ *   together with VD_STEP_LCM, VD_STEP_DPM or VD_STEP_UNIPC it is VD_EINVAL; vd_ddim_cfg_step
+ *   refuses it, as any bit it does not know; with VD_STEP_PAG it combines exactly as plain Euler
+ *   does, the PAG scales in front of the rows and the low byte 2 or 3): the diffusers
+ *   EulerAncestralDiscreteScheduler.step update (epsilon prediction) instead of Euler's, after the
+ *   unchanged guidance / PAG combine, in the same one-rounding-per-op fp32 arithmetic, in exactly
+ *   this order:
+ *     x0 = x - sigma*eps
+ *     d  = (x - x0) / sigma
+ *     x  <- x + d*(sigma_down - sigma)
+ *     x  <- x + noise*sigma_up                       (only if sigma_up != 0)
+ *     next_in <- bf16(x / sqrt(sigma_to^2 + 1)) per branch, the padding columns zero
+ *   both divisions correctly rounded; x0_out is optional and receives x0, as without the flag.
+ *   It rides on this entry point instead of a new symbol, as VD_STEP_LCM rides on
+ *   vd_ddim_cfg_step, and the per-step noise travels in coef the same way: one fp32 buffer,
+ *   16-byte aligned (else VD_EINVAL), of
+ *     n_coef rows of 4 floats {sigma, sigma_down, sqrt(sigma_to^2 + 1), sigma_up} — Euler's row
+ *       with sigma_next replaced by sigma_down and its unused zero by sigma_up (sigma_to is the
+ *       schedule's next sigma; sigma_up^2 + sigma_down^2 = sigma_to^2), then
+ *     n_coef slabs of B*C*F*H*W floats in (B,C,F,H,W) order, from float offset 4*n_coef.
+ *   Step st (= *step_idx clamped to the n_coef rows) reads row st and, only when that row's
+ *   sigma_up != 0, slab st: the last step of every schedule has sigma_to = 0, hence sigma_up =
+ *   sigma_down = 0, so its slab is sized but never read, and whatever it holds, NaN included,
+ *   reaches no output.  A plain Euler table (sigma_down = sigma_next, slot 3 = 0) under the flag
+ *   therefore gives the unflagged kernel's result bit for bit.  Step index, row and noise are all
+ *   read inside the launch, so a captured step replays over the whole schedule.  This library
+ *   cannot check the buffer's size; the caller does (vdiff.ops.euler_ancestral_cfg_step).
  * VD_STEP_PAG OR-ed into ncfg (0x800) of vd_ddim_cfg_step — alone, or with VD_STEP_LCM,
- *   VD_STEP_DPM or VD_STEP_UNIPC — or of vd_euler_cfg_step: perturbed-attention guidance (diffusers' PAGMixin).  The
+ *   VD_STEP_DPM or VD_STEP_UNIPC — or of vd_euler_cfg_step, alone or with VD_STEP_ANCESTRAL:
+ *   perturbed-attention guidance (diffusers' PAGMixin).  The
  *   low byte is then 2 or 3 (anything else is VD_EINVAL; without the flag 3 stays VD_EINVAL):
  *     3: eps rows [uncond; cond; perturbed], each of B*F*H*W rows,
  *          e = (e_u + g*(e_c - e_u)) + s*(e_c - e_p)
@@ -575,8 +603,9 @@ int vd_lpips_pairs(const void* frames_u8, int64_t videos, int32_t frames, int32_
  *     n_coef fp32 PAG scales, padded with (-n_coef mod 4) floats to a multiple of 4 (the padding
  *       is never read), then
  *     the scheduler's unchanged layout, from float offset 4*ceil(n_coef/4): n_coef rows of 4
- *       (DDIM, Euler), 8 (LCM, DPM) or 16 (UniPC) floats and, where that scheduler has them, its n_coef noise
- *       slabs behind the rows.  The padding keeps the 16-byte alignment LCM and DPM ask for.
+ *       (DDIM, Euler, Euler ancestral), 8 (LCM, DPM) or 16 (UniPC) floats and, where that scheduler
+ *       has them, its n_coef noise slabs behind the rows.  The padding keeps the 16-byte alignment
+ *       LCM, DPM, UniPC and Euler ancestral ask for.
  *   s = pag[st], st the same clamped device step index that picks the coefficient row, read inside
  *   the launch.  The scales must be finite and >= 0; this library cannot read device memory, so
  *   the caller checks that (vdiff.ops.pag_coef does).  next_in receives one copy of the packed
@@ -588,6 +617,7 @@ enum { VD_STEP_LCM = 0x100 }; /* OR-ed into vd_ddim_cfg_step's ncfg, see above *
 enum { VD_STEP_DPM = 0x400 }; /* likewise; x0_out becomes the in/out history, see above */
 enum { VD_STEP_PAG = 0x800 }; /* into either step's ncfg: a third branch, scales in front of coef */
 enum { VD_STEP_UNIPC = 0x2000 }; /* as VD_STEP_DPM; x0_out becomes the in/out three-slab state, see above */
+enum { VD_STEP_ANCESTRAL = 0x4000 }; /* into vd_euler_cfg_step's ncfg: the stochastic step, noise slabs behind the rows */
 int vd_timestep_embed(const float* ts, int64_t n_ts, const int32_t* step_idx, int64_t B,
                       int32_t dim, void* out, vd_stream_t stream);
 int vd_pack_latents(const float* x, int64_t B, int64_t C, int64_t F, int64_t H, int64_t W,

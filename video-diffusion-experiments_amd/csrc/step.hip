@@ -13,7 +13,9 @@
 // coefficient rows in the same device buffer (lcm_cfg_kernel); with VD_STEP_DPM the
 // DPMSolverMultistepScheduler update, whose history travels in x0_out (dpm_cfg_kernel); with
 // VD_STEP_UNIPC the UniPCMultistepScheduler update, corrector and predictor in one pass, whose
-// three state slabs travel in x0_out (unipc_cfg_kernel).
+// three state slabs travel in x0_out (unipc_cfg_kernel).  vd_euler_cfg_step likewise takes
+// VD_STEP_ANCESTRAL: the EulerAncestralDiscreteScheduler update, its per-step noise behind the
+// rows as LCM's (euler_a_cfg_kernel).
 #include "common.h"
 
 namespace {
@@ -168,6 +170,48 @@ __global__ void euler_cfg_kernel(const float* eps, int64_t ld_eps, int ncfg, flo
     const float x0 = x - sig * e;
     const float d = div_rn(x - x0, sig);
     const float xn = x + d * dt;
+    lat[i] = xn;
+    if (x0_out) x0_out[i] = x0;
+    if (next_in) write_next_in(next_in, f2bf(div_rn(xn, in_div)), r, c, half_rows, ncfg, C, cpad);
+  }
+}
+
+// CFG combine + diffusers:EulerAncestralDiscreteScheduler.step (epsilon prediction), in diffusers'
+// fp32 operation order (vd_euler_cfg_step with VD_STEP_ANCESTRAL in ncfg):
+//   x0 = x - sigma*eps;  d = (x - x0) / sigma;  x <- x + d * (sigma_down - sigma)
+//   x <- x + noise * sigma_up                    (only where sigma_up != 0)
+// and the next step's UNet input = x / sqrt(sigma_to^2 + 1).  coef holds n_coef rows of 4 floats
+// {sigma, sigma_down, sqrt(sigma_to^2 + 1), sigma_up} — Euler's row with sigma_next replaced and
+// its unused zero filled — and, from float 4 * n_coef on, n_coef noise slabs of B*C*F*HW floats in
+// latent order, as LCM's.  Row and noise are read here by the device step index, so one captured
+// launch serves the whole schedule.  A slab whose row has sigma_up == 0 (the last step of every
+// schedule) is never read, so an Euler table under the flag gives euler_cfg_kernel's result.
+__global__ void euler_a_cfg_kernel(const float* eps, int64_t ld_eps, int ncfg, float g, float* lat,
+                                   int64_t B, int64_t C, int64_t F, int64_t HW, const float* coef,
+                                   int64_t n_coef, const int32_t* step_idx, float* x0_out, bf16_t* next_in,
+                                   int64_t cpad, const float* pag) {
+#pragma clang fp contract(off)  // one rounding per operation, as torch's separate fp32 ops
+  const int st = table_row(step_idx, n_coef);
+  const float pag_s = pag ? pag[st] : 0.f;
+  const float sig = coef[4 * st + 0], sig_d = coef[4 * st + 1], in_div = coef[4 * st + 2];
+  const float sig_up = coef[4 * st + 3];
+  const bool add_noise = sig_up != 0.f;
+  const float dt = sig_d - sig;
+  const int64_t total = B * C * F * HW;
+  const int64_t half_rows = B * F * HW;
+  const float* noise = coef + 4 * n_coef + (int64_t)st * total;
+  for (int64_t i = (int64_t)blockIdx.x * NT + threadIdx.x; i < total; i += (int64_t)gridDim.x * NT) {
+    const int64_t p = i % HW;
+    const int64_t f = (i / HW) % F;
+    const int64_t c = (i / (HW * F)) % C;
+    const int64_t b = i / (HW * F * C);
+    const int64_t r = (b * F + f) * HW + p;
+    const float e = guided_eps(eps, ld_eps, r, c, half_rows, ncfg, g, pag != nullptr, pag_s);
+    const float x = lat[i];
+    const float x0 = x - sig * e;
+    const float d = div_rn(x - x0, sig);
+    float xn = x + d * dt;
+    if (add_noise) xn = xn + noise[i] * sig_up;
     lat[i] = xn;
     if (x0_out) x0_out[i] = x0;
     if (next_in) write_next_in(next_in, f2bf(div_rn(xn, in_div)), r, c, half_rows, ncfg, C, cpad);
@@ -437,12 +481,22 @@ extern "C" int vd_euler_cfg_step(const float* eps, int64_t ld_eps, int32_t ncfg,
                                  float* latents, int64_t B, int64_t C, int64_t F, int64_t H,
                                  int64_t W, const float* coef, int64_t n_coef, const int32_t* step_idx,
                                  float* x0_out, void* next_in, int64_t cpad, vd_stream_t stream) {
-  // VD_STEP_PAG is the one flag Euler takes; VD_STEP_LCM / VD_STEP_DPM / VD_STEP_UNIPC fail the low-byte check
+  // VD_STEP_PAG and VD_STEP_ANCESTRAL are the flags Euler takes; VD_STEP_LCM / VD_STEP_DPM /
+  // VD_STEP_UNIPC and any other high bit fail the low-byte check, with or without them
+  const bool ancestral = (ncfg & VD_STEP_ANCESTRAL) != 0;
+  ncfg &= ~VD_STEP_ANCESTRAL;
   const float* pag;
   if (const int rc = split_pag_coef(ncfg, coef, n_coef, pag)) return rc;
   VD_CHECK_ARG(eps && latents && coef && n_coef > 0 && ld_eps >= C);
   VD_CHECK_ARG(pag ? (ncfg == 2 || ncfg == 3) : (ncfg == 1 || ncfg == 2));
   if (next_in) VD_CHECK_ARG(cpad >= C);
+  if (ancestral) {
+    VD_CHECK_ARG(B > 0 && C > 0 && F > 0 && H > 0 && W > 0 && ((uintptr_t)coef & 15) == 0);
+    hipLaunchKernelGGL(euler_a_cfg_kernel, dim3(grid_for(B * C * F * H * W)), dim3(NT), 0,
+                       (hipStream_t)stream, eps, ld_eps, ncfg, guidance, latents, B, C, F, H * W,
+                       coef, n_coef, step_idx, x0_out, (bf16_t*)next_in, cpad, pag);
+    return vd_launch_status();
+  }
   hipLaunchKernelGGL(euler_cfg_kernel, dim3(grid_for(B * C * F * H * W)), dim3(NT), 0,
                      (hipStream_t)stream, eps, ld_eps, ncfg, guidance, latents, B, C, F, H * W,
                      coef, n_coef, step_idx, x0_out, (bf16_t*)next_in, cpad, pag);

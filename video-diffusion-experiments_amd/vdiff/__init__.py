@@ -20,7 +20,8 @@ from .pipeline import (AnimateDiffControlNetPipeline, AnimateDiffPAGPipeline, An
                        AnimateDiffVideoToVideoPipeline, ControlNetConditioning, DenoiseLoop,
                        PerturbedAttentionGuidance, SparseControlConditioning)
 from .sched import (DDIMScheduler, DDIMSchedulerOutput, DPMSolverMultistepScheduler,  # noqa: F401
-                    DPMSolverMultistepSchedulerOutput, EulerDiscreteScheduler, EulerDiscreteSchedulerOutput,
+                    DPMSolverMultistepSchedulerOutput, EulerAncestralDiscreteScheduler,
+                    EulerAncestralDiscreteSchedulerOutput, EulerDiscreteScheduler, EulerDiscreteSchedulerOutput,
                     LCMScheduler, LCMSchedulerOutput, UniPCMultistepScheduler, UniPCMultistepSchedulerOutput)
 from .tokenizer import CLIPTokenizer  # noqa: F401
 from .weights import init_synthetic_, load_diffusers_state_dict  # noqa: F401

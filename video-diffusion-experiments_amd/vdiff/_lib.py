@@ -21,6 +21,7 @@ VD_STEP_LCM = 0x100  # OR-ed into vd_ddim_cfg_step's ncfg: the LCMScheduler upda
 VD_STEP_DPM = 0x400  # likewise: the DPMSolverMultistepScheduler update, x0_out its in/out history
 VD_STEP_PAG = 0x800  # into either step's ncfg: perturbed-attention guidance, its scales in front of coef
 VD_STEP_UNIPC = 0x2000  # as VD_STEP_DPM: the UniPCMultistepScheduler update, x0_out its in/out three-slab state
+VD_STEP_ANCESTRAL = 0x4000  # into vd_euler_cfg_step's ncfg: the EulerAncestralDiscreteScheduler update, noise behind the rows
 
 # Every exported symbol and its argtypes: the single source of truth used by the
 # loader and by tests/test_abi.py (which checks it against include/vdiff.h).

@@ -246,6 +246,9 @@ class DiTDenoiseLoop:
         if getattr(scheduler, "kind", "ddim") == "unipc":
             raise NotImplementedError("UniPCMultistepScheduler with DiTDenoiseLoop is not supported: this loop "
                                       "drives the DDIM schedule and holds no multistep state")
+        if getattr(scheduler, "kind", "ddim") == "euler_a":
+            raise NotImplementedError("EulerAncestralDiscreteScheduler with DiTDenoiseLoop is not supported: this "
+                                      "loop holds no per-step noise slabs")
         self.coef = scheduler.coefficient_table(torch.as_tensor(ts).cpu()).to(dev)
         self.sched_step = ops.SCHED_STEP[getattr(scheduler, "kind", "ddim")]
         if getattr(scheduler, "kind", "ddim") != "ddim":

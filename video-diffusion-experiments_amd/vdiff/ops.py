@@ -942,8 +942,41 @@ def unipc_cfg_step(eps, ncfg, guidance, latents, coef, step_idx=None, x0_out=Non
           "vd_ddim_cfg_step (VD_STEP_UNIPC)")
 
 
+STEP_ANCESTRAL = 0x4000  # VD_STEP_ANCESTRAL, OR-ed into vd_euler_cfg_step's ncfg
+EULER_A_ROW = 4          # floats per Euler-ancestral coefficient row
+
+
+def euler_a_buffer_numel(n_steps, latent_numel):
+    """Floats of the Euler-ancestral coef buffer: n_steps rows of EULER_A_ROW, then n_steps noise slabs."""
+    return n_steps * (EULER_A_ROW + latent_numel)
+
+
+def euler_ancestral_cfg_step(eps, ncfg, guidance, latents, coef, step_idx=None, x0_out=None, next_in=None,
+                             pag_n=0):
+    """CFG combine + EulerAncestralDiscreteScheduler.step (+ next input's scale_model_input), fused
+    (vd_euler_cfg_step with VD_STEP_ANCESTRAL).  `coef` is the rows-plus-slabs buffer of
+    include/vdiff.h: n rows of 4 floats {sigma, sigma_down, sqrt(sigma_to^2 + 1), sigma_up}, then n
+    noise slabs of latents.numel() floats; n is derived from its size.  x0_out receives x0."""
+    _dev(eps, latents, coef, step_idx, x0_out, next_in)
+    if latents.dtype != torch.float32 or not latents.is_contiguous():
+        raise ValueError("latents must be contiguous fp32")
+    if coef.dtype != torch.float32 or not coef.is_contiguous():
+        raise ValueError("euler_ancestral_cfg_step: coef must be a contiguous fp32 buffer")
+    ncfg, body = _pag_split("euler_ancestral_cfg_step", coef, pag_n, ncfg)
+    per = EULER_A_ROW + latents.numel()
+    if body.numel() == 0 or body.numel() % per:
+        raise ValueError(f"euler_ancestral_cfg_step: coef holds {body.numel()} floats, not a multiple of "
+                         f"{EULER_A_ROW} + {latents.numel()} (rows, then one noise slab per row)")
+    _pag_rows("euler_ancestral_cfg_step", body.numel() // per, pag_n)
+    B, Cc, Fr, H, W = latents.shape
+    check(lib().vd_euler_cfg_step(_p(eps), eps.stride(0), ncfg | STEP_ANCESTRAL, guidance, _p(latents), B, Cc, Fr,
+                                  H, W, _p(coef), body.numel() // per, _p(step_idx), _p(x0_out), _p(next_in),
+                                  next_in.shape[1] if next_in is not None else 0, _stream()),
+          "vd_euler_cfg_step (VD_STEP_ANCESTRAL)")
+
+
 SCHED_STEP = {"ddim": ddim_cfg_step, "euler": euler_cfg_step, "lcm": lcm_cfg_step, "dpm": dpm_cfg_step,
-              "unipc": unipc_cfg_step}
+              "unipc": unipc_cfg_step, "euler_a": euler_ancestral_cfg_step}
 
 
 def step_advance(step_idx):

@@ -61,6 +61,10 @@ step kernel runs the previous step's corrector and this step's predictor in one 
 holds its state — the last two x0 predictions and the sample the previous predictor started from —
 in the three slabs of `unipc_state`, read and overwritten in place like `x0_hist`.
 
+With a `vdiff.EulerAncestralDiscreteScheduler` ("Euler a") the Euler step goes down to sigma_down and
+adds noise of scale sigma_up: one noise slab per step, drawn up front in diffusers' order and kept
+behind the 4-float rows as LCM's are (`VD_STEP_ANCESTRAL` on the Euler step kernel).
+
 AnimateDiffControlNetPipeline (diffusers' third AnimateDiff pipeline) conditions the video on
 per-frame control images: a `vdiff.ControlNetModel` runs on the step's input inside the same
 captured graph and its 13 residuals are added to the UNet's skips and mid-block output by
@@ -214,7 +218,8 @@ class DenoiseLoop:
         """step_noise (a stochastic scheduler only, where it is required): the noise of the
         stochastic steps in step order.  LCM: [n_steps - 1 or n_steps, B, C, F, H, W] (the last
         step adds none; a row given for it is ignored).  The SDE type of
-        DPMSolverMultistepScheduler: [n_steps, B, C, F, H, W], every step adds noise.  It lives
+        DPMSolverMultistepScheduler and EulerAncestralDiscreteScheduler: [n_steps, B, C, F, H, W], one
+        slab per step (Euler ancestral's last step reads none: its sigma_up is 0).  It lives
         behind the coefficient rows in one device buffer that the step kernel reads by the device
         step index, so the captured graph serves any later reset(latents, step_noise=...).
         ip_embeds: the projected IP-Adapter image tokens [Bt, n, cross_attention_dim] (uncond
@@ -298,6 +303,18 @@ class DenoiseLoop:
             self.noise_slabs.zero_()
             self.coef_rows.copy_(rows)
             self._fill_step_noise(step_noise)
+        elif self.kind == "euler_a":
+            # LCM's layout behind rows of 4; a slab is read unless its row's sigma_up is 0 (the last step's)
+            if step_noise is None:
+                raise ValueError("an Euler-ancestral DenoiseLoop needs step_noise: the noise of its stochastic "
+                                 f"steps, [{self.n_steps}, {', '.join(map(str, self.lat.shape))}]")
+            self.coef = torch.empty(ops.euler_a_buffer_numel(self.capacity, self.lat.numel()), device=dev,
+                                    dtype=torch.float32)
+            self.coef_rows = self.coef[:ops.EULER_A_ROW * self.capacity].view(self.capacity, ops.EULER_A_ROW)
+            self.noise_slabs = self.coef[ops.EULER_A_ROW * self.capacity:].view(self.capacity, *self.lat.shape)
+            self.noise_slabs.zero_()
+            self.coef_rows.copy_(rows)
+            self._fill_step_noise(step_noise)
         else:
             if step_noise is not None:
                 raise ValueError("step_noise is for an LCM scheduler or the SDE type of DPMSolverMultistepScheduler; "
@@ -325,7 +342,7 @@ class DenoiseLoop:
                 self.noise_slabs = body[width * self.capacity:].view(self.capacity, *self.lat.shape)
             self.step_kwargs["pag_n"] = self.capacity
         self.in_div0 = 1.0
-        if self.kind == "euler":
+        if self.kind in ("euler", "euler_a"):
             self.in_div0 = scheduler.input_divisor(scheduler.index_for_timestep(float(torch.as_tensor(ts)[0])))
         self.step_idx = torch.zeros(1, device=dev, dtype=torch.int32)
         self.control = control
@@ -434,7 +451,8 @@ class DenoiseLoop:
         """Copy the schedule's step noise into the slabs behind the coefficient rows."""
         want = tuple(self.lat.shape)
         sn = torch.as_tensor(step_noise)
-        counts = (self.n_steps,) if self.dpm_sde else (self.n_steps - 1, self.n_steps)
+        # one slab per step for the SDE type of DPM and for Euler ancestral, whose draw order has one per step
+        counts = (self.n_steps,) if self.dpm_sde or self.kind == "euler_a" else (self.n_steps - 1, self.n_steps)
         if sn.dim() != 6 or tuple(sn.shape[1:]) != want or sn.shape[0] not in counts:
             raise ValueError(f"step_noise of shape {tuple(sn.shape)}: expected [{' or '.join(map(str, counts))}, "
                              f"{', '.join(map(str, want))}] (one slab per stochastic step, in step order)")
@@ -442,10 +460,10 @@ class DenoiseLoop:
 
     def reset(self, latents, step_noise=None):
         """Back to step 0 with new latents; a loop with step noise (LCM, the SDE type of
-        DPMSolverMultistepScheduler) also takes the new run's step_noise (None keeps the slabs it
+        DPMSolverMultistepScheduler, Euler ancestral) also takes the new run's step_noise (None keeps the slabs it
         holds).  A multistep loop's history needs no clearing: step 0 never reads it."""
         if step_noise is not None:
-            if self.kind != "lcm" and not self.dpm_sde:
+            if self.kind not in ("lcm", "euler_a") and not self.dpm_sde:
                 raise ValueError("step_noise is for an LCM scheduler or the SDE type of DPMSolverMultistepScheduler; "
                                  f"this loop's is {self.kind!r}")
             self._fill_step_noise(step_noise)
@@ -466,7 +484,7 @@ class DenoiseLoop:
             raise ValueError(f"reschedule: {n} timesteps, the loop's tables were built for 1..{self.capacity}")
         self.ts[:n].copy_(ts.to(self.ts.device, torch.float32))
         self.coef_rows[:n].copy_(self.scheduler.coefficient_table(ts.cpu()).to(self.coef.device))
-        if self.kind == "euler":
+        if self.kind in ("euler", "euler_a"):
             self.in_div0 = self.scheduler.input_divisor(self.scheduler.index_for_timestep(float(ts[0])))
         if self.pag is not None:  # the new timesteps' PAG scales
             self.pag_tab[:n].copy_(ops.pag_scales(self.pag.table(ts)))
@@ -828,6 +846,10 @@ class AnimateDiffPipeline:
     def _dpm_sde(self) -> bool:
         return self._dpm and self.scheduler.sde
 
+    @property
+    def _euler_a(self) -> bool:
+        return getattr(self.scheduler, "kind", None) == "euler_a"
+
     def _refuse_scheduler_combinations(self):
         """What a stochastic or multistep scheduler does not combine with."""
         if self._lcm and self.dist is not None:
@@ -837,6 +859,9 @@ class AnimateDiffPipeline:
             raise NotImplementedError("DPMSolverMultistepScheduler's algorithm_type 'sde-dpmsolver++' with a "
                                       "frame-sharded pipeline (dist=) is not supported: the per-step noise slabs are "
                                       "not sharded over the ranks' frames ('dpmsolver++' is)")
+        if self._euler_a and self.dist is not None:
+            raise NotImplementedError("EulerAncestralDiscreteScheduler with a frame-sharded pipeline (dist=) is not "
+                                      "supported: the per-step noise slabs are not sharded over the ranks' frames")
         if self._dpm and self.free_init_enabled:
             raise NotImplementedError("FreeInit with DPMSolverMultistepScheduler is not supported: diffusers' "
                                       "add_noise at a timestep outside the schedule falls back to the last sigma; "
@@ -853,6 +878,8 @@ class AnimateDiffPipeline:
         dtype the initial noise is drawn in (diffusers draws in model_output.dtype, the pipeline's
         torch_dtype).  The SDE type of DPMSolverMultistepScheduler: [n_steps, *latents.shape], one
         fp32 draw per step, the last included (diffusers draws there too, and multiplies by 0).
+        EulerAncestralDiscreteScheduler: [n_steps, *latents.shape], one draw per step in the pipeline's
+        torch_dtype as for LCM, the last included (diffusers draws there too; its sigma_up is 0).
         Either way that is the draw order of diffusers' loop, where scheduler.step is the only
         thing that draws.  draw=False gives zeros of that shape (a loop built before its noise is
         known)."""
@@ -861,6 +888,12 @@ class AnimateDiffPipeline:
                 return torch.zeros((n_steps,) + tuple(latents.shape), device=latents.device, dtype=torch.float32)
             return torch.stack([randn_tensor(latents.shape, generator=generator, device=latents.device,
                                              dtype=torch.float32) for _ in range(n_steps)])
+        if self._euler_a:
+            if not draw:
+                return torch.zeros((n_steps,) + tuple(latents.shape), device=latents.device, dtype=torch.float32)
+            dtype = self.torch_dtype or torch.float32
+            return torch.stack([randn_tensor(latents.shape, generator=generator, device=latents.device, dtype=dtype)
+                                for _ in range(n_steps)]).to(torch.float32)
         if not self._lcm:
             return None
         shape = (max(n_steps - 1, 0),) + tuple(latents.shape)

@@ -224,11 +224,12 @@ def load_tokenizer(tok_dir):
 def load_scheduler(sched_dir):
     """The pipeline's scheduler from scheduler_config.json.  SD-1.5 ships PNDMScheduler, which the
     reference immediately replaces (05:136-141 DDIM, 01/03 Euler) from `pipe.scheduler.config`;
-    DDIM / Euler / LCM configs build that class, anything else a DDIMScheduler holding the same config
+    DDIM / Euler / Euler-ancestral / LCM configs build that class, anything else a DDIMScheduler holding the same config
     (its unknown keys are kept in `.config` so the reference's from_config(...) sees them)."""
-    from .sched import DDIMScheduler, EulerDiscreteScheduler, LCMScheduler
+    from .sched import DDIMScheduler, EulerAncestralDiscreteScheduler, EulerDiscreteScheduler, LCMScheduler
     cfg = read_json(Path(sched_dir) / "scheduler_config.json")
-    cls = {"EulerDiscreteScheduler": EulerDiscreteScheduler, "LCMScheduler": LCMScheduler}.get(
+    cls = {"EulerDiscreteScheduler": EulerDiscreteScheduler, "LCMScheduler": LCMScheduler,
+           "EulerAncestralDiscreteScheduler": EulerAncestralDiscreteScheduler}.get(
         cfg.get("_class_name"), DDIMScheduler)
     s = cls.from_config({k: v for k, v in cfg.items() if not k.startswith("_")})
     s.source_config = cfg

@@ -48,14 +48,14 @@ DEFAULT_CONFIG = dict(
 )
 
 
-class EulerDiscreteScheduler:
+class _EulerSchedule:
+    """What EulerDiscreteScheduler and EulerAncestralDiscreteScheduler (euler_ancestral.py) share:
+    the training sigmas, the inference timesteps and interpolated sigmas, scale_model_input,
+    add_noise and the step-index rules.  A subclass sets `config`, calls `_init_sigmas` and
+    provides `coefficients(i)` and `step`."""
     order = 1
-    kind = "euler"
 
-    def __init__(self, **kwargs):
-        cfg = dict(DEFAULT_CONFIG)
-        cfg.update({k: v for k, v in kwargs.items() if k in cfg})
-        self.config = _Cfg(cfg)
+    def _init_sigmas(self, cfg):
         n = cfg["num_train_timesteps"]
         if cfg["trained_betas"] is not None:
             betas = torch.tensor(cfg["trained_betas"], dtype=torch.float32)
@@ -65,10 +65,6 @@ class EulerDiscreteScheduler:
             betas = torch.linspace(cfg["beta_start"] ** 0.5, cfg["beta_end"] ** 0.5, n, dtype=torch.float32) ** 2
         else:
             raise NotImplementedError(cfg["beta_schedule"])
-        if (cfg["prediction_type"] != "epsilon" or cfg["use_karras_sigmas"] or cfg["rescale_betas_zero_snr"]
-                or cfg["interpolation_type"] != "linear" or cfg["final_sigmas_type"] != "zero"):
-            raise NotImplementedError("only the SD-1.5 epsilon / linear-interpolation configuration the "
-                                      "reference runs")
         self.betas = betas
         self.alphas = 1.0 - betas
         self.alphas_cumprod = torch.cumprod(self.alphas, dim=0)
@@ -143,12 +139,6 @@ class EulerDiscreteScheduler:
             self._init_step_index(timestep)
         return sample / self.input_divisor(self._step_index)
 
-    def coefficients(self, i: int) -> torch.Tensor:
-        """fp32 {sigma_i, sigma_{i+1}, sqrt(sigma_{i+1}^2 + 1), 0} for step index i (the last
-        step's next-input divisor is that of sigma = 0, i.e. 1)."""
-        s, sn = self.sigmas[i], self.sigmas[i + 1]
-        return torch.stack([s, sn, sqrt32(sn ** 2 + 1), torch.zeros(())]).float()
-
     def coefficient_table(self, timesteps=None) -> torch.Tensor:
         """Rows for the given schedule timesteps (default: the whole schedule), indexed by
         the pipeline's device step counter; a timestep repeated past the schedule (the
@@ -166,6 +156,31 @@ class EulerDiscreteScheduler:
         idx = [self.index_for_timestep(v) for v in t.tolist()]
         sigma = self.sigmas[idx].to(x.device).reshape((-1,) + (1,) * (x.dim() - 1))
         return x + noise.to(x.device, torch.float32) * sigma
+
+    def __len__(self):
+        return self.config.num_train_timesteps
+
+
+class EulerDiscreteScheduler(_EulerSchedule):
+    kind = "euler"
+
+    def __init__(self, **kwargs):
+        cfg = dict(DEFAULT_CONFIG)
+        cfg.update({k: v for k, v in kwargs.items() if k in cfg})
+        self.config = _Cfg(cfg)
+        if cfg["trained_betas"] is None and cfg["beta_schedule"] not in ("linear", "scaled_linear"):
+            raise NotImplementedError(cfg["beta_schedule"])
+        if (cfg["prediction_type"] != "epsilon" or cfg["use_karras_sigmas"] or cfg["rescale_betas_zero_snr"]
+                or cfg["interpolation_type"] != "linear" or cfg["final_sigmas_type"] != "zero"):
+            raise NotImplementedError("only the SD-1.5 epsilon / linear-interpolation configuration the "
+                                      "reference runs")
+        self._init_sigmas(cfg)
+
+    def coefficients(self, i: int) -> torch.Tensor:
+        """fp32 {sigma_i, sigma_{i+1}, sqrt(sigma_{i+1}^2 + 1), 0} for step index i (the last
+        step's next-input divisor is that of sigma = 0, i.e. 1)."""
+        s, sn = self.sigmas[i], self.sigmas[i + 1]
+        return torch.stack([s, sn, sqrt32(sn ** 2 + 1), torch.zeros(())]).float()
 
     def step(self, model_output, timestep, sample, s_churn: float = 0.0, s_tmin: float = 0.0,
              s_tmax: float = float("inf"), s_noise: float = 1.0, generator=None, return_dict: bool = True):
@@ -188,7 +203,3 @@ class EulerDiscreteScheduler:
         if not return_dict:
             return (prev,)
         return EulerDiscreteSchedulerOutput(prev_sample=prev, pred_original_sample=x0)
-
-    def __len__(self):
-        return self.config.num_train_timesteps
-
