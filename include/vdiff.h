@@ -773,6 +773,30 @@ int vd_block_transpose(const void* src, void* dst, int64_t nb, int64_t na, int64
  *   byte; C != 8; K or F outside 1..256; hw < 1; rows not a multiple of F * hw; x or out NULL or
  *   not 16-byte aligned; out == x; ldx or ldo below 8 or not a multiple of 8; y NULL, misaligned,
  *   y_f32 != 1 or not inside a device allocation (hipPointerGetAttributes, as op 7).
+ *   Op 9, VD_ROWS_PROMPT_LERP, is FreeNoise's prompt travel (diffusers'
+ *   AnimateDiffFreeNoiseMixin._encode_prompt_free_noise with its default linear
+ *   prompt_interpolation_callback: the key prompts' embeddings interpolated frame by frame), riding
+ *   here for the same reason as ops 2-8.  The op word is the plain op: nothing rides above the low
+ *   byte.  Geometry, as op 8's: F = y_period frames, L = y_div tokens per prompt, K = ldy key prompts
+ *   per video, rows = B * F * L OUTPUT rows of C columns.  x = bf16 key rows of stride ldx >= C, key
+ *   k of video b, token l at row (b * K + k) * L + l.  y = K int32 frame indices in DEVICE memory,
+ *   4-byte aligned, y_f32 == 1, read inside the launch only, shared by all videos; they must be
+ *   strictly increasing with idx[0] == 0 and idx[K - 1] == F - 1 (the host wrapper's duty: the
+ *   entry point cannot check device values).  For video b, frame f, token l, with k the LARGEST
+ *   index whose idx[k] <= f:
+ *     out[(b * F + f) * L + l] = x[(b * K + k) * L + l], bit for bit,            if f == idx[k],
+ *                                bf16( fmaf(w, B, (1.0f - w) * A) ) per element  otherwise,
+ *     A = float(x[(b * K + k) * L + l]), B = float(x[(b * K + k + 1) * L + l]),
+ *     w = float(f - idx[k]) / float(idx[k + 1] - idx[k]), one correctly rounded fp32 division;
+ *   1.0f - w and (1.0f - w) * A are rounded to fp32, then one fused multiply-add and one rounding
+ *   to bf16.  16-byte chunks, no atomics, every output element written; out may be a column slice
+ *   of a wider buffer.  The result of video b depends on its own keys and the table alone.  A
+ *   table that breaks the contract never makes the kernel read outside x: k and k + 1 are clamped
+ *   into [0, K - 1] before addressing (the values are then unspecified).
+ *   VD_EINVAL, before any launch: any bit above the op byte; K or F outside 1..256; L < 1; rows not
+ *   a multiple of F * L; C % 8; x or out NULL or not 16-byte aligned; out == x; ldx or ldo below C
+ *   or not a multiple of 8; y NULL, misaligned, y_f32 != 1 or not inside a device allocation
+ *   (hipPointerGetAttributes, as ops 7 and 8).
  * vd_upsample_nearest2x: rows of n_img h x w images -> rows of their nearest x2 upsample
  *   (Upsample2D's F.interpolate(scale_factor=2.0, mode="nearest")). */
 enum {
@@ -784,7 +808,8 @@ enum {
   VD_ROWS_WIN_MERGE = 5,
   VD_ROWS_SPECTRAL = 6,
   VD_ROWS_CTRL_ADD = 7,
-  VD_ROWS_SPARSE_COND = 8
+  VD_ROWS_SPARSE_COND = 8,
+  VD_ROWS_PROMPT_LERP = 9
 };
 #define VD_ROWS_WIN_STRIDE(s) ((s) << 8)
 #define VD_ROWS_SPEC_PASS(p) ((p) << 8)

@@ -28,7 +28,7 @@ __device__ __forceinline__ void load8_any(const void* p, int is_f32, float* f) {
 // op 1: out[r] = silu(x[r])
 // op 3: out[r] = x[r] * *y                                        (y one fp32 on the device)
 // (op 2 is freeu_filter_kernel, ops 4 and 5 win_gather_kernel / win_merge_kernel, op 7 ctrl_add_kernel,
-// op 8 sparse_cond_kernel below)
+// op 8 sparse_cond_kernel, op 9 prompt_lerp_kernel below)
 __global__ void rows_eltwise_kernel(int op, const bf16_t* x, int64_t ldx, const void* y, int64_t ldy, int y_f32,
                                     int64_t y_div, int64_t y_period, int64_t rows, int64_t C, bf16_t* out,
                                     int64_t ldo) {
@@ -362,6 +362,55 @@ __global__ __launch_bounds__(NT) void sparse_cond_kernel(const bf16_t* x, int64_
   }
 }
 
+// op 9, FreeNoise prompt travel: out row (b, f, l) <- the key prompts' token row l, interpolated
+// linearly between the two key frames around f (include/vdiff.h).  Every workgroup first copies the
+// K indices into LDS and turns them into a frame -> (k, exact) table and a frame -> weight table there
+// (thread f scans the indices in ascending k and keeps the last k with idx[k] <= f: at most K <= 256
+// broadcast LDS reads, once per workgroup), then one lane per 16-byte chunk does
+// one load and a copy on a key frame, two loads and eight fused multiply-adds elsewhere.  k and
+// k + 1 are clamped into [0, K - 1], so a table that breaks the contract reads inside x.
+constexpr int PROMPT_MAX = 256;  // the longest F and K: F <= NT fills the tables in one pass
+__global__ __launch_bounds__(NT) void prompt_lerp_kernel(const bf16_t* x, int64_t ldx, const int* idx, int K, int F,
+                                                         int64_t L, int64_t rows, int64_t C, bf16_t* out,
+                                                         int64_t ldo) {
+  __shared__ int kof[PROMPT_MAX];    // 2 * k + (f == idx[k])
+  __shared__ float wof[PROMPT_MAX];  // float(f - idx[k]) / float(idx[k + 1] - idx[k])
+  __shared__ int sidx[PROMPT_MAX];   // the K indices: one global load each, the scans below read LDS
+  for (int k = threadIdx.x; k < K; k += NT) sidx[k] = idx[k];
+  __syncthreads();
+  for (int f = threadIdx.x; f < F; f += NT) {
+    int ks = 0;
+    for (int k = 0; k < K; ++k)
+      if (sidx[k] <= f) ks = k;
+    const int lo = sidx[ks], hi = sidx[min(ks + 1, K - 1)];
+    kof[f] = 2 * ks + (lo == f ? 1 : 0);
+    wof[f] = (float)(f - lo) / (float)(hi - lo);
+  }
+  __syncthreads();
+  const int64_t cpr = C / 8;
+  const int64_t total = rows * cpr;
+  for (int64_t i = (int64_t)blockIdx.x * NT + threadIdx.x; i < total; i += (int64_t)gridDim.x * NT) {
+    const int64_t r = i / cpr;
+    const int64_t c = (i - r * cpr) * 8;
+    const int64_t bf = r / L, l = r - bf * L, b = bf / F;
+    const int f = (int)(bf - b * F);
+    const int ke = kof[f], ka = ke >> 1, kb = min(ka + 1, K - 1);
+    const uint4 ua = *(const uint4*)(x + ((b * K + ka) * L + l) * ldx + c);
+    uint4 v = ua;
+    if (!(ke & 1)) {
+      const uint4 ub = *(const uint4*)(x + ((b * K + kb) * L + l) * ldx + c);
+      const float w = wof[f], u = 1.0f - w;
+      float ea[8], eb[8];
+      unpack8(ua, ea);
+      unpack8(ub, eb);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) ea[j] = fmaf(w, eb[j], u * ea[j]);
+      v = pack8(ea);
+    }
+    *(uint4*)(out + r * ldo + c) = v;
+  }
+}
+
 unsigned grid_for(int64_t total) {
   const int64_t b = (total + NT - 1) / NT;
   return (unsigned)(b < 16384 ? (b > 0 ? b : 1) : 16384);
@@ -422,6 +471,19 @@ extern "C" int vd_rows_eltwise(int32_t op, const void* x, int64_t ldx, const voi
     VD_CHECK_ARG(y && ((uintptr_t)y & 3) == 0 && y_f32 == 1 && on_device(y));
     hipLaunchKernelGGL(sparse_cond_kernel, dim3(grid_for(rows)), dim3(NT), 0, (hipStream_t)stream, (const bf16_t*)x,
                        ldx, (const int*)y, (int)K, (int)F, hw, (int)cc, rows, (bf16_t*)out, ldo);
+    return vd_launch_status();
+  }
+  // op 9 carries nothing above the low byte; the K indices are DEVICE memory, as op 8's
+  if (op >= 0 && (op & 0xff) == VD_ROWS_PROMPT_LERP) {
+    const int64_t F = y_period, L = y_div, K = ldy;
+    VD_CHECK_ARG((op >> 8) == 0 && C > 0 && C % 8 == 0);
+    VD_CHECK_ARG(K >= 1 && K <= PROMPT_MAX && F >= 1 && F <= PROMPT_MAX && L >= 1 && rows > 0 && L <= rows);
+    VD_CHECK_ARG(rows % (F * L) == 0);
+    VD_CHECK_ARG(x && out && al16(x) && al16(out) && x != out);
+    VD_CHECK_ARG(ldx >= C && ldo >= C && ldx % 8 == 0 && ldo % 8 == 0);
+    VD_CHECK_ARG(y && ((uintptr_t)y & 3) == 0 && y_f32 == 1 && on_device(y));
+    hipLaunchKernelGGL(prompt_lerp_kernel, dim3(grid_for(rows * (C / 8))), dim3(NT), 0, (hipStream_t)stream,
+                       (const bf16_t*)x, ldx, (const int*)y, (int)K, (int)F, L, rows, C, (bf16_t*)out, ldo);
     return vd_launch_status();
   }
   // ops 4 and 5 carry the window stride above the low byte (VD_ROWS_WIN_STRIDE); no other op does

@@ -33,6 +33,18 @@ from .layers import (Act, Attention, Conv2d, Downsample2D, Dropout, FeedForward,
 Transformer2DModelOutput = namedtuple("Transformer2DModelOutput", ["sample"])
 
 
+def text_rows_per_frame(n_rows, batch, frames, ctx_len):
+    """Whether n_rows text rows are the per-frame form (batch * frames * ctx_len: FreeNoise prompt
+    travel) or the per-video form (batch * ctx_len); the two coincide at one frame.  Any other
+    count is a ValueError."""
+    if n_rows == batch * ctx_len:
+        return False
+    if n_rows == batch * frames * ctx_len:
+        return True
+    raise ValueError(f"{n_rows} text rows: expected {batch} videos x {ctx_len} tokens, or "
+                     f"{batch} x {frames} frames x {ctx_len} tokens in the per-frame form")
+
+
 class Ctx:
     """Per-forward state shared by every block (fast path)."""
 
@@ -40,8 +52,15 @@ class Ctx:
         self.batch = batch            # videos in this forward (2 with CFG)
         self.frames = frames          # frames held by THIS rank
         self.temb_all = temb_all      # fp32 [batch, sum(resnet Cout)] = time_emb_proj(silu(temb))
-        self.ehs_rows = ehs_rows      # bf16 [batch*ctx_len, D]
+        self.ehs_rows = ehs_rows      # bf16 [batch*ctx_len, D], or [batch*frames*ctx_len, D] per frame
         self.ctx_len = ctx_len
+        # FreeNoise prompt travel: every frame reads its own text, rows (video, frame, token); the
+        # cross-attention's K/V are then addressed by the image (kv_div 1) and not by the video
+        self.text_per_frame = ehs_rows is not None and text_rows_per_frame(ehs_rows.shape[0], batch, frames, ctx_len)
+        if self.text_per_frame and (dist is not None or ip_rows is not None):
+            raise NotImplementedError("per-frame text together with " +
+                                      ("frame sharding (dist=)" if dist is not None else "IP-Adapter image tokens") +
+                                      " is not supported: those row layouts are per video")
         self.ip_rows = ip_rows        # bf16 [batch*n, D]: IP-Adapter image tokens, or None
         self.dist = dist              # vdiff.dist.FrameShard or None
         self.kv_cache = kv_cache      # {id(attn): kv rows} or None
@@ -279,17 +298,19 @@ class BasicTransformerBlock(nn.Module):
                 kv = self.attn2.project_kv(ctx.ehs_rows, ctx.ip_rows, ctx.batch)
             if ctx.kv_cache is not None:
                 ctx.kv_cache[id(self.attn2)] = kv
+        # per-frame text (FreeNoise prompt travel): image i reads K/V rows [i * ctx_len, (i + 1) * ctx_len)
+        kv_div = 1 if ctx.text_per_frame else ctx.frames
         if dup:  # the cross-attention of each guidance half on the shared q: no copy of q or h
             L, Mh = kv.shape[0] // 2, h.shape[0]
             a = torch.empty(2 * Mh, C, device=h.device, dtype=h.dtype)
             for g in range(2):
                 ops.attention(q, kv[g * L:(g + 1) * L, :C], kv[g * L:(g + 1) * L, C:], n_img, self.heads, hw,
-                              skv, d, kv_div=ctx.frames, scale=self.attn2.attn_scale, out=a[g * Mh:(g + 1) * Mh],
+                              skv, d, kv_div=kv_div, scale=self.attn2.attn_scale, out=a[g * Mh:(g + 1) * Mh],
                               **tail)
             h, n = self._out_norm_dup(a, self.attn2, 3, h)
         else:
             a = ops.attention(q, kv[:, :C], kv[:, C:], n_img, self.heads, hw, skv, d,
-                              kv_div=ctx.frames, scale=self.attn2.attn_scale, **tail)
+                              kv_div=kv_div, scale=self.attn2.attn_scale, **tail)
             h, n = self._out_norm(a, self.attn2, 3, h)
         return self._ff(h, n)
 

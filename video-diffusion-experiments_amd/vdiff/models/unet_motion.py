@@ -397,11 +397,14 @@ class UNetMotionModel(nn.Module):
         emb = self.time_embedding(self.time_proj(t))                       # (B, 1280)
         emb = ops.rows_add(None, emb, y_div=Fr, out=torch.empty(B * Fr, emb.shape[1], device=emb.device,
                                                                 dtype=torch.bfloat16))  # repeat_interleave(F)
-        ehs_rows = token_rows(ehs)
-        ehs_rep = torch.empty(B * Fr * L, ehs.shape[2], device=ehs.device, dtype=torch.bfloat16)
-        for b in range(B):  # ehs.repeat_interleave(F, 0)
-            ops.rows_add(None, ehs_rows[b * L:(b + 1) * L], out=ehs_rep[b * Fr * L:(b + 1) * Fr * L])
-        ehs_rep = ehs_rep.view(B * Fr, L, -1)
+        if ehs.shape[0] == B * Fr:  # per-frame text (or one frame): the rows are (video, frame) already
+            ehs_rep = ehs
+        else:
+            ehs_rows = token_rows(ehs)
+            ehs_rep = torch.empty(B * Fr * L, ehs.shape[2], device=ehs.device, dtype=torch.bfloat16)
+            for b in range(B):  # ehs.repeat_interleave(F, 0)
+                ops.rows_add(None, ehs_rows[b * L:(b + 1) * L], out=ehs_rep[b * Fr * L:(b + 1) * Fr * L])
+            ehs_rep = ehs_rep.view(B * Fr, L, -1)
         x = sample.permute(0, 2, 1, 3, 4).reshape(B * Fr, Cc, H, W)
         h = self.conv_in(x)
         skips = (h,)
@@ -442,13 +445,20 @@ class UNetMotionModel(nn.Module):
         t = t.to(torch.float32).expand(B).contiguous()
         ehs = encoder_hidden_states.to(device=dev, dtype=torch.bfloat16).contiguous()
         L = ehs.shape[1]
+        # B rows of text, or B * F in the per-frame form (FreeNoise prompt travel), video-major
+        if ehs.dim() != 3 or ehs.shape[0] not in (B, B * Fr):
+            raise ValueError(f"encoder_hidden_states of shape {tuple(ehs.shape)}: expected {B} rows (one per video) "
+                             f"or {B * Fr} (one per frame, video-major) of [tokens, dim]")
+        if ehs.shape[0] != B and getattr(self, "dist", None) is not None:
+            raise NotImplementedError("per-frame text together with frame sharding (dist=) is not supported: "
+                                      "the text row layout is per video")
         control = self._control_residuals(down_block_additional_residuals, mid_block_additional_residual,
                                           B * Fr, H, W)
         if self.has_hooks():
             out = self.forward_modules(sample.to(dev, torch.float32), t, ehs, control=control)
         else:
             te = ops.timestep_embed(t, self.time_proj.num_channels)
-            ctx = self.make_ctx(te, ehs.reshape(B * L, -1), B, Fr, L)
+            ctx = self.make_ctx(te, ehs.reshape(ehs.shape[0] * L, -1), B, Fr, L)
             x_rows = ops.pack_latents(sample.to(dev), dup=1, cpad=CIN_PAD)
             eps_rows = self.forward_rows(x_rows, H, W, ctx, control=control)
             out = ops.unpack_nhwc(eps_rows, B, self.config["out_channels"], Fr, H, W)

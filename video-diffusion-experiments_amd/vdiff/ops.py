@@ -1204,6 +1204,52 @@ def sparse_cond(key_rows, idx, B, F, hw, cc, out=None):
     return out
 
 
+ROWS_PROMPT_LERP = 9         # VD_ROWS_PROMPT_LERP
+PROMPT_MAX = 256             # the longest F and K
+
+
+def prompt_frame_indices(idx, F):
+    """The key frames of a prompt travel: ints, strictly increasing, the first 0, the last F - 1
+    (encode_prompt_free_noise appends the last prompt there); refused before any device work."""
+    idx = idx.tolist() if torch.is_tensor(idx) else list(idx)
+    for i in idx:
+        if isinstance(i, bool) or not isinstance(i, int):
+            raise TypeError(f"prompt_lerp: frame index {i!r} is not an integer")
+    if not 1 <= len(idx) <= PROMPT_MAX or not 1 <= F <= PROMPT_MAX:
+        raise ValueError(f"prompt_lerp: 1..{PROMPT_MAX} key prompts and frames, got {len(idx)} and {F}")
+    if any(b <= a for a, b in zip(idx, idx[1:])):
+        raise ValueError(f"prompt_lerp: frame indices {idx} are not strictly increasing")
+    if idx[0] != 0:
+        raise ValueError(f"prompt_lerp: the first frame index must be 0, got {idx[0]}")
+    if idx[-1] != F - 1:
+        raise ValueError(f"prompt_lerp: the last frame index must be {F - 1} (the last of {F} frames), got {idx[-1]}")
+    return idx
+
+
+def prompt_lerp(key_rows, idx, B, F, L, out=None):
+    """FreeNoise prompt travel (vd_rows_eltwise op 9): key_rows holds K = len(idx) key prompts per
+    video as bf16 rows (b, k, token) of C columns, L tokens each; the result is the [B * F * L, C]
+    per-frame rows (b, f, token): frame idx[k] is key k bit for bit, a frame between two keys their
+    linear interpolation, w = (f - idx[k]) / (idx[k + 1] - idx[k]), one rounding to bf16.  One
+    launch writes every element; out may be a column slice of a wider buffer."""
+    frames = prompt_frame_indices(idx, F)
+    K = len(frames)
+    if L < 1 or B < 1 or key_rows.dim() != 2 or key_rows.shape[0] != B * K * L or key_rows.shape[1] % 8:
+        raise ValueError(f"prompt_lerp: key rows of shape {tuple(key_rows.shape)} are not {B} videos x {K} key prompts "
+                         f"x {L} tokens of C % 8 == 0 columns")
+    _dev(key_rows, out)
+    C = key_rows.shape[1]
+    if out is None:
+        out = torch.empty(B * F * L, C, device=key_rows.device, dtype=BF16)
+    if tuple(out.shape) != (B * F * L, C):
+        raise ValueError(f"prompt_lerp: out of shape {tuple(out.shape)}, {B} videos of {F} frames need "
+                         f"{(B * F * L, C)}")
+    idx_dev = torch.tensor(frames, dtype=torch.int32, device=key_rows.device)
+    check(lib().vd_rows_eltwise(ROWS_PROMPT_LERP, _p(key_rows), _rows(key_rows), _p(idx_dev), K, 1, L, F,
+                                out.shape[0], C, _p(out), _rows(out), _stream()), "vd_rows_eltwise(prompt_lerp)")
+    return out
+
+
 ROWS_SPECTRAL = 6            # VD_ROWS_SPECTRAL
 ROWS_SPEC_PASS_SHIFT = 8     # VD_ROWS_SPEC_PASS(p) = p << 8, p in 1..5
 SPECTRAL_MAX = 256           # VD_SPECTRAL_MAX: the longest F, H or W

@@ -243,7 +243,20 @@ class DenoiseLoop:
         cfg_shard (vdiff.dist.CfgShard, CFG only): this rank runs the UNet on ONE half
         (cfg_shard.index: 0 uncond, 1 cond) and swaps eps rows with its pair before the
         fused CFG+scheduler update, which both ranks apply to their replicated latents
-        (SURVEY.md §8e (ii)).  prompt_embeds still holds both halves, uncond first."""
+        (SURVEY.md §8e (ii)).  prompt_embeds still holds both halves, uncond first.
+        prompt_embeds: [Bt, L, D], Bt the guidance branches times the videos, or the per-frame form
+        [Bt * F, L, D] (FreeNoise prompt travel, AnimateDiffPipeline.encode_prompt_free_noise): rows
+        (branch, video, frame), every frame's spatial cross-attention reads its own text.  The K/V
+        cache is still filled once per loop and is F times larger.  Not supported with ip_embeds,
+        cfg_shard, pag or frame sharding, whose text row layouts are per video."""
+        n_br = (2 if guidance_scale > 1 else 1) + (pag is not None)
+        if latents.shape[2] > 1 and prompt_embeds.shape[0] == n_br * latents.shape[0] * latents.shape[2]:
+            what = ("ip_embeds (IP-Adapter)" if ip_embeds is not None else "cfg_shard" if cfg_shard is not None else
+                    "perturbed-attention guidance (pag=)" if pag is not None else
+                    "frame sharding (dist=)" if getattr(unet, "dist", None) is not None else None)
+            if what is not None:  # before any device work
+                raise NotImplementedError(f"per-frame text (prompt travel) together with {what} is not supported: "
+                                          "the text + image K/V rows and the sharded text rows are laid out per video")
         if not unet._prepared:
             unet.prepare()
         dev = unet.device
@@ -365,17 +378,21 @@ class DenoiseLoop:
             # the step counter moves into the control block's header (ops.ctrl_block)
             self.ctrl_block, self.step_idx = ops.ctrl_block(control.table(self.capacity, self.cn_res), dev)
         pe = prompt_embeds.to(dev, torch.bfloat16).contiguous()
-        if pe.shape[0] != self.Bt:
+        if pe.shape[0] not in (self.Bt, self.Bt * self.F):
             raise ValueError(f"prompt_embeds batch {pe.shape[0]} != {self.Bt} (uncond first when CFG; with pag= the "
-                             "conditional embeddings once more at the end)")
+                             f"conditional embeddings once more at the end), or {self.Bt * self.F} in the per-frame "
+                             "form (FreeNoise prompt travel: video-major, then frame)")
         self.L = pe.shape[1]
+        # per-frame text (FreeNoise prompt travel): F text entries per video, so F times the K/V rows
+        # in the cross-attention cache, still projected once per loop
+        self.text_frames = self.F if pe.shape[0] != self.Bt else 1
         # the UNet batch: both CFG halves, or this rank's half under cfg_shard
         self.Bu = self.Bt
         if self.cfg_shard is not None:
             h = self.cfg_shard.index
             pe = pe[h * self.B:(h + 1) * self.B].contiguous()
             self.Bu = self.B
-        self.ehs_rows = pe.reshape(self.Bu * self.L, -1)
+        self.ehs_rows = pe.reshape(self.Bu * self.text_frames * self.L, -1)
         self.ip_rows = None
         if ip_embeds is not None:
             if self.cfg_shard is not None:
@@ -400,7 +417,8 @@ class DenoiseLoop:
             half = self.B * self.F * self.H * self.W
             self.cn_cond_rows = cond if self.cn_batch == self.B else torch.cat([cond, cond])
             self.cn_x_in = self.x_in[half:] if self.cn_cond_only else self.x_in
-            self.cn_ehs_rows = self.ehs_rows[self.B * self.L:] if self.cn_cond_only else self.ehs_rows
+            self.cn_ehs_rows = (self.ehs_rows[self.B * self.text_frames * self.L:] if self.cn_cond_only
+                                else self.ehs_rows)
             self.cn_kv_cache = {}
         # the FreeU scalars the step's launches (and the graph) read: kept alive for this loop's
         # life, whatever enable_freeu / disable_freeu does to the blocks afterwards
@@ -706,8 +724,9 @@ class AnimateDiffPipeline:
         if noise_type not in self.FREE_NOISE_NOISE_TYPES:
             raise ValueError(f"noise_type {noise_type!r}: one of {self.FREE_NOISE_NOISE_TYPES}")
         if prompt_interpolation_callback is not None:
-            raise NotImplementedError("prompt_interpolation_callback (FreeNoise prompt travel) is not supported: "
-                                      "per-frame text embeddings need per-frame cross-attention K/V")
+            raise NotImplementedError("a custom prompt_interpolation_callback is not supported: FreeNoise prompt "
+                                      "travel (a {frame: text} prompt) interpolates linearly, diffusers' default, "
+                                      "on the device (vd_rows_eltwise op 9)")
         self.unet.enable_free_noise(context_length, context_stride, weighting_scheme)
         m = self.unet.motion_modules_in_order()[0]
         self._free_noise = (m.context_length, m.context_stride, noise_type)
@@ -1045,6 +1064,117 @@ class AnimateDiffPipeline:
         hs = enc(ids, output_hidden_states=True).hidden_states
         return enc.text_model.final_layer_norm(hs[-(clip_skip + 1)])
 
+    @staticmethod
+    def _prompt_travel_keys(prompt, num_frames, name="prompt"):
+        """diffusers' _encode_prompt_free_noise normalisation of one side: a str is {0: str}; int
+        keys, str values; sorted by frame; the first key 0, the last <= num_frames - 1, where the
+        last prompt is repeated when no key names it -> (frame indices, texts)."""
+        if isinstance(prompt, str):
+            prompt = {0: prompt}
+        if not isinstance(prompt, dict):
+            raise ValueError(f"Expected `{name}` to be either `str` or `dict`, got {type(prompt).__name__}.")
+        if not prompt or not all(isinstance(k, int) and not isinstance(k, bool) for k in prompt) or \
+                not all(isinstance(v, str) for v in prompt.values()):
+            raise ValueError(f"Expected integer keys and string values for `{name}` dict.")
+        frames = sorted(prompt)
+        if frames[0] != 0:
+            raise ValueError(f"The minimum frame index in `{name}` dict must be 0 or missing.")
+        if frames[-1] >= num_frames:
+            raise ValueError(f"The maximum frame index in `{name}` dict must be lesser than `num_frames` and follow "
+                             "0-based indexing.")
+        texts = [prompt[f] for f in frames]
+        if frames[-1] != num_frames - 1:
+            frames, texts = frames + [num_frames - 1], texts + [texts[-1]]
+        return frames, texts
+
+    def encode_prompt_free_noise(self, prompt, negative_prompt, num_frames, num_videos_per_prompt=1,
+                                 do_classifier_free_guidance=True, clip_skip=None):
+        """diffusers' AnimateDiffFreeNoiseMixin._encode_prompt_free_noise with its default linear
+        interpolation (FreeNoise prompt travel): `prompt` is a str or a {frame: text} dict, and so
+        is `negative_prompt`, with keys of its own.  Every key prompt of both sides goes through
+        the text encoder in ONE batched forward; each side's [K, 77, dim] key embeddings are
+        interpolated frame by frame by one launch (ops.prompt_lerp, vd_rows_eltwise op 9).
+        -> (prompt_embeds, negative_prompt_embeds or None), each bf16 [num_videos_per_prompt,
+        num_frames, 77, dim] on the UNet's device: the per-frame form __call__ takes as prompt_embeds /
+        negative_prompt_embeds; flattened over (video, frame) it is DenoiseLoop's per-frame form."""
+        pf, pt = self._prompt_travel_keys(prompt, num_frames)
+        nf, nt = [], []
+        if do_classifier_free_guidance:
+            nf, nt = self._prompt_travel_keys("" if negative_prompt is None else negative_prompt, num_frames,
+                                              "negative_prompt")
+        keys = self.encode_prompt(nt + pt, len(nt) + len(pt), clip_skip=clip_skip)
+        keys = keys.to(self.unet.device, torch.bfloat16).contiguous()
+        L, D = keys.shape[1], keys.shape[2]
+
+        def travel(k, frames):
+            rows = ops.prompt_lerp(k.reshape(len(frames) * L, D), frames, 1, num_frames, L)
+            return rows.view(1, num_frames, L, D).repeat(num_videos_per_prompt, 1, 1, 1)
+
+        pos = travel(keys[len(nt):], pf)
+        return pos, (travel(keys[:len(nt)], nf) if do_classifier_free_guidance else None)
+
+    @staticmethod
+    def _is_per_frame(e):
+        """Precomputed embeddings in the per-frame form are 4-D, [videos, F, tokens, dim]; 3-D ones
+        are per video, [videos, tokens, dim], as they always were."""
+        return e is not None and e.dim() == 4
+
+    def _refuse_prompt_dict(self, prompt, negative_prompt):
+        """A {frame: text} dict needs FreeNoise; refused before any tokenizer or device work."""
+        if (isinstance(prompt, dict) or isinstance(negative_prompt, dict)) and not self.free_noise_enabled:
+            raise NotImplementedError("a {frame: text} prompt dict (FreeNoise prompt travel) needs FreeNoise: call "
+                                      "enable_free_noise() first")
+
+    def _prompt_travel_ehs(self, prompt, negative_prompt, prompt_embeds, negative_prompt_embeds, num_frames, do_cfg,
+                           num_videos_per_prompt, clip_skip, ip_given, unused):
+        """The per-frame text of a prompt-travel call -> (ehs [Bt * F, L, D] with the unconditional
+        half first under CFG, B), or None for a call in today's per-video form.  A call is a
+        prompt-travel call when a prompt is a dict or precomputed embeddings are per frame."""
+        travel = isinstance(prompt, dict) or isinstance(negative_prompt, dict)
+        pre = self._is_per_frame(prompt_embeds) or self._is_per_frame(negative_prompt_embeds)
+        if not travel and not pre:
+            return None
+        if not self.free_noise_enabled:
+            raise NotImplementedError("per-frame prompt embeddings (FreeNoise prompt travel) need FreeNoise: call "
+                                      "enable_free_noise() first")
+        if ip_given:
+            raise NotImplementedError("FreeNoise prompt travel together with an IP-Adapter image prompt is not "
+                                      "supported: the text + image K/V rows are laid out per video")
+        if unused.get("cfg_shard") is not None:
+            raise NotImplementedError("FreeNoise prompt travel together with cfg_shard is not supported")
+        if self.dist is not None:
+            raise NotImplementedError("FreeNoise prompt travel with a frame-sharded pipeline (dist=) is not supported")
+        pos, neg = prompt_embeds, negative_prompt_embeds
+        if pos is None or (do_cfg and neg is None):
+            if pos is None and prompt is None:
+                raise ValueError("prompt or prompt_embeds required")
+            if isinstance(prompt, (list, tuple)) or isinstance(negative_prompt, (list, tuple)):
+                raise ValueError("Expected `prompt` and `negative_prompt` to be either `str` or `dict` in a "
+                                 "prompt-travel call (one travel per call, as diffusers).")
+            p, n = self.encode_prompt_free_noise(prompt if pos is None else "", negative_prompt, num_frames,
+                                                 num_videos_per_prompt, do_cfg and neg is None, clip_skip)
+            pos = p if pos is None else pos
+            neg = n if neg is None else neg
+        dev = self.unet.device
+
+        def form(e, what, repeat):
+            e = e.to(dev, torch.bfloat16)
+            if not self._is_per_frame(e):  # per-video beside a per-frame side: every frame reads the same text
+                e = e[:, None].expand(-1, num_frames, -1, -1)
+            if e.shape[1] != num_frames:
+                raise ValueError(f"{what} of shape {tuple(e.shape)}: the per-frame form is [videos, {num_frames}, "
+                                 "tokens, dim]")
+            return e.repeat_interleave(num_videos_per_prompt, 0) if repeat else e
+
+        pos = form(pos, "prompt_embeds", prompt_embeds is not None)
+        B = pos.shape[0]
+        if do_cfg:
+            neg = form(neg, "negative_prompt_embeds", negative_prompt_embeds is not None)
+            if neg.shape != pos.shape:
+                raise ValueError(f"negative embeddings of shape {tuple(neg.shape)} for positive {tuple(pos.shape)}")
+            pos = torch.cat([neg, pos])
+        return pos.reshape(-1, pos.shape[2], pos.shape[3]).contiguous(), B
+
     @torch.no_grad()
     def decode_latents(self, latents):
         """diffusers AnimateDiffPipeline.decode_latents: latents / scaling_factor, frames
@@ -1100,9 +1230,7 @@ class AnimateDiffPipeline:
             raise NotImplementedError("FreeInit with a frame-sharded pipeline (dist=) is not supported: the filter "
                                       "needs every frame of a video and the ranks would have to agree on z_rand")
         self._refuse_scheduler_combinations()
-        if isinstance(prompt, dict) or isinstance(negative_prompt, dict):
-            raise NotImplementedError("a {frame: text} prompt dict (FreeNoise prompt travel) is not supported: "
-                                      "per-frame text embeddings need per-frame cross-attention K/V")
+        self._refuse_prompt_dict(prompt, negative_prompt)
         if output_type not in ("latent", "pt", "np", "pil"):
             raise NotImplementedError(f"output_type {output_type!r}: use 'pil', 'pt', 'np' or 'latent'")
         if output_type != "latent" and self.vae is None:
@@ -1112,7 +1240,11 @@ class AnimateDiffPipeline:
         h = (height or sample * 8) // 8
         w = (width or sample * 8) // 8
         do_cfg = guidance_scale > 1
-        if prompt_embeds is None:
+        # FreeNoise prompt travel: per-frame text, [Bt * F, L, D] for the loop
+        travel = self._prompt_travel_ehs(prompt, negative_prompt, prompt_embeds, negative_prompt_embeds, num_frames,
+                                         do_cfg, num_videos_per_prompt, clip_skip,
+                                         ip_adapter_image is not None or ip_adapter_image_embeds is not None, unused)
+        if travel is None and prompt_embeds is None:
             if prompt is None:
                 raise ValueError("prompt or prompt_embeds required")
             pos = [prompt] if isinstance(prompt, str) else list(prompt)
@@ -1128,14 +1260,17 @@ class AnimateDiffPipeline:
                 prompt_embeds = both[n:]
             else:
                 prompt_embeds = self.encode_prompt(pos, n, clip_skip=clip_skip)
-        B = prompt_embeds.shape[0] * num_videos_per_prompt
-        prompt_embeds = prompt_embeds.repeat_interleave(num_videos_per_prompt, 0)
-        if do_cfg:
-            if negative_prompt_embeds is None:
-                negative_prompt_embeds = self.encode_prompt(negative_prompt or "", B, clip_skip=clip_skip)
-            ehs = torch.cat([negative_prompt_embeds.to(prompt_embeds), prompt_embeds])
+        if travel is not None:
+            ehs, B = travel
         else:
-            ehs = prompt_embeds
+            B = prompt_embeds.shape[0] * num_videos_per_prompt
+            prompt_embeds = prompt_embeds.repeat_interleave(num_videos_per_prompt, 0)
+            if do_cfg:
+                if negative_prompt_embeds is None:
+                    negative_prompt_embeds = self.encode_prompt(negative_prompt or "", B, clip_skip=clip_skip)
+                ehs = torch.cat([negative_prompt_embeds.to(prompt_embeds), prompt_embeds])
+            else:
+                ehs = prompt_embeds
         ip_embeds = self.prepare_ip_adapter_image_embeds(ip_adapter_image, ip_adapter_image_embeds,
                                                          B // num_videos_per_prompt, num_videos_per_prompt, do_cfg)
         self.scheduler.set_timesteps(num_inference_steps)
@@ -1280,29 +1415,42 @@ class AnimateDiffVideoToVideoPipeline(AnimateDiffPipeline):
         if video is None and latents is None:
             raise ValueError("video or latents required")
         self._refuse_scheduler_combinations()
-        if isinstance(prompt, dict) or isinstance(negative_prompt, dict):
-            raise NotImplementedError("a {frame: text} prompt dict (FreeNoise prompt travel) is not supported: "
-                                      "per-frame text embeddings need per-frame cross-attention K/V")
+        self._refuse_prompt_dict(prompt, negative_prompt)
         do_cfg = guidance_scale > 1
-        if prompt_embeds is None:
-            if prompt is None:
-                raise ValueError("prompt or prompt_embeds required")
-            pos = [prompt] if isinstance(prompt, str) else list(prompt)
-            prompt_embeds = self.encode_prompt(pos, len(pos), clip_skip=clip_skip)
-        B = prompt_embeds.shape[0] * num_videos_per_prompt
-        prompt_embeds = prompt_embeds.repeat_interleave(num_videos_per_prompt, 0)
-        if do_cfg:
-            if negative_prompt_embeds is None:
-                negative_prompt_embeds = self.encode_prompt(negative_prompt or "", B, clip_skip=clip_skip)
-            ehs = torch.cat([negative_prompt_embeds.to(prompt_embeds), prompt_embeds])
+        # FreeNoise prompt travel: per-frame text over the frames the video (or the latents) has
+        travel = None
+        if isinstance(prompt, dict) or isinstance(negative_prompt, dict) or self._is_per_frame(prompt_embeds) or \
+                self._is_per_frame(negative_prompt_embeds):
+            if latents is None:  # the frame count comes from the video: preprocessed here, once
+                video = preprocess_video(video, height, width)
+            nf = latents.shape[2] if latents is not None else video.shape[2]
+            travel = self._prompt_travel_ehs(prompt, negative_prompt, prompt_embeds, negative_prompt_embeds, nf,
+                                             do_cfg, num_videos_per_prompt, clip_skip,
+                                             ip_adapter_image is not None or ip_adapter_image_embeds is not None,
+                                             unused)
+        if travel is not None:
+            ehs, B = travel
         else:
-            ehs = prompt_embeds
+            if prompt_embeds is None:
+                if prompt is None:
+                    raise ValueError("prompt or prompt_embeds required")
+                pos = [prompt] if isinstance(prompt, str) else list(prompt)
+                prompt_embeds = self.encode_prompt(pos, len(pos), clip_skip=clip_skip)
+            B = prompt_embeds.shape[0] * num_videos_per_prompt
+            prompt_embeds = prompt_embeds.repeat_interleave(num_videos_per_prompt, 0)
+            if do_cfg:
+                if negative_prompt_embeds is None:
+                    negative_prompt_embeds = self.encode_prompt(negative_prompt or "", B, clip_skip=clip_skip)
+                ehs = torch.cat([negative_prompt_embeds.to(prompt_embeds), prompt_embeds])
+            else:
+                ehs = prompt_embeds
         ip_embeds = self.prepare_ip_adapter_image_embeds(ip_adapter_image, ip_adapter_image_embeds,
                                                          B // num_videos_per_prompt, num_videos_per_prompt, do_cfg)
         self.scheduler.set_timesteps(num_inference_steps)
         ts, _ = self.get_timesteps(num_inference_steps, strength)
         if latents is None:
-            video = preprocess_video(video, height, width)
+            if travel is None:
+                video = preprocess_video(video, height, width)
             if video.shape[0] == 1 and B > 1:
                 video = video.expand(B, -1, -1, -1, -1)
             if video.shape[0] != B:
